@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- GenomicsBench hot kernels on MI355X (driver contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batches B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batches B] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it packs the 'large' phmm job, runs one
+checked pass and the W warm-up steps, times exactly K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the result line. --full adds everything else described below (the
+fmi / chain / bsw legs, the 'small' sets, the human-scale fmi index, CPU baselines and their parity
+checks, drop-in end-to-end timings, shard proxies, the N-rank gathered-output check); the options that
+shape those parts (--only, --no-small, --no-cpu-baseline, --no-e2e, --shard-of, ...) act under --full
+(GB_BENCH_FULL=1 in the environment is the same switch, for scripts that make several bench.py calls).
+--dump-outputs DIR: DIR/phmm_<name>.npy, what a caller of the timed path receives from its last timed
+step (log10 results f64, raw f32, raw f64, the fallback choice as f32; rank 0's shard). The job is
+seeded, so the same arguments give the same inputs on every run and two builds compare array for array.
 
 Metric (BASELINE.json): "GCUPS (phmm) + Mreads/s (fmi) on 'large' set at 1/2/4/8 MI355X".
 phmm (the line's `value`): a step = one PairHMM forward pass (f32 kernel + f64 fallback kernel +
@@ -619,6 +630,46 @@ def cpu_baseline_bsw(pairs, params, sample_seconds: float, gpu=None):
             "parity_check": check}
 
 
+DUMP_MAX_BYTES = 60_000_000  # of array data; the files and their headers stay under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays: dict, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """--dump-outputs: every array of `arrays` (all of one length, one entry per unit of the job) as
+    out_dir/<name>.npy, f64 kept and everything else as f32. Together they stay under max_bytes: a larger
+    set is cut to the same sample of units in every array (sorted indices drawn with a fixed seed, so
+    the set's length alone decides them)."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+            for k, v in arrays.items()}
+    n = len(next(iter(conv.values()))) if conv else 0
+    per_unit = sum(a.dtype.itemsize for a in conv.values())
+    keep = n if n * per_unit <= max_bytes else max_bytes // per_unit
+    sel = None if keep == n else np.sort(np.random.default_rng(20240229).choice(n, keep, replace=False))
+    for k, a in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a if sel is None else a[sel])
+    return {"dir": out_dir, "arrays": sorted(conv), "units": int(keep), "of": int(n),
+            "bytes": int(keep * per_unit)}
+
+
+def write_detail(line: dict, detail: str):
+    """The full record as JSON at `detail` (relative: under the repository). A tree or folder that
+    cannot be written (a read-only checkout) must not cost the run its result line: the record then
+    goes to the temporary directory. Returns the path written (as given when it was usable), or None."""
+    import tempfile
+    d = detail if os.path.isabs(detail) else os.path.join(ROOT, detail)
+    for path, shown in ((d, detail), (os.path.join(tempfile.gettempdir(), os.path.basename(d)),) * 2):
+        try:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(line, f)
+        except OSError as e:
+            log(f"full bench record: cannot write {shown} ({e.strerror})")
+            continue
+        log(f"full bench record: {shown} ({len(json.dumps(line))} bytes)")
+        return shown
+    return None
+
+
 def set_seed(args, base: int, rank: int) -> int:
     """Strong scaling: one set for the whole job (every rank the same seed, then its shard); weak:
     every rank its own full-size set."""
@@ -1183,6 +1234,12 @@ def bench_phmm(args, D, rank, world, kind="large"):
         return a
     elapsed, ms32 = timed_steps(D, args.steps, job.run, after)
     ms64 = float(np.mean(k64)) if k64 else 0.0
+    dumped = None
+    if args.dump_outputs and kind == "large" and rank == 0:
+        d_res, d_rf, d_rd, d_used, _ = job.results()  # of the last timed step
+        dumped = dump_outputs(args.dump_outputs, {"phmm_log10": d_res[:ta.n], "phmm_raw_f32": d_rf[:ta.n],
+                                                  "phmm_raw_f64": d_rd[:ta.n], "phmm_used_double": d_used[:ta.n]})
+        log(f"phmm: last timed step's outputs written to {args.dump_outputs} ({dumped['bytes']} bytes)")
     cells_all = D.sum(float(cells))
     gcups = cells_all * args.steps / elapsed / 1e9
     # the f32 pass's early exit drops testcases proven to fall back before their last rows: its
@@ -1211,6 +1268,7 @@ def bench_phmm(args, D, rank, world, kind="large"):
         # testcases' rows): what the step would be without the f64 fallback (its 36 % share of
         # testcases is a property of the synthetic generator)
         "f32_only_gcups": cells / max(ms32 * 1e-3, 1e-12) / 1e9,
+        "outputs_dumped": dumped,
     }
     if world > 1:
         def full_pass(w):
@@ -1746,8 +1804,16 @@ def main():
                     help="print the N rank processes' command and environment that --gpus N would start, then exit")
     ap.add_argument("--no-rank-check", action="store_true",
                     help="world > 1: skip the gathered-output check against a 1-rank pass on rank 0")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", default=os.environ.get("GB_BENCH_FULL", "0") not in ("", "0"),
+                    help="(or GB_BENCH_FULL=1, for a script that sets it once for all its bench.py calls) "
+                         "also run everything beyond the headline's timed phmm steps: the fmi / chain / bsw legs, "
+                         "the 'small' sets, human-scale fmi, CPU baselines and parity checks, drop-in end-to-end "
+                         "timings, shard proxies, the N-rank gathered-output check (the options below that shape "
+                         "those parts need it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (rank 0) as DIR/phmm_*.npy")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: one set sharded over the ranks (default); weak: a full set per rank")
     ap.add_argument("--batches", type=int, default=64, help="'large' phmm batches in the job")
@@ -1781,6 +1847,15 @@ def main():
     args.shard_of = max(args.shard_ns) if args.shard_ns else 0
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if not args.full:
+        # a plain run: the 'large' phmm job's warm-up and timed steps, nothing that takes runs of its own
+        if args.only and set(args.only.split(",")) != {"phmm"}:
+            raise SystemExit(f"--only {args.only}: legs other than phmm need --full")
+        args.only = "phmm"
+        args.no_small = args.no_cpu_baseline = args.no_e2e = args.no_rank_check = True
+        args.shard_ns, args.shard_of = [], 0
     if "WORLD_SIZE" in os.environ:
         if int(os.environ["WORLD_SIZE"]) != args.gpus:
             print(f"bench.py: WORLD_SIZE={os.environ['WORLD_SIZE']} (from the launcher) does not match "
@@ -1864,12 +1939,10 @@ def main():
         }
         add_per_core(line)
         detail = args.detail_out
+        if not args.full and detail == ap.get_default("detail_out"):
+            detail = ""  # a plain run writes a record only where --detail-out names one
         if detail:
-            d = detail if os.path.isabs(detail) else os.path.join(ROOT, detail)
-            os.makedirs(os.path.dirname(d), exist_ok=True)
-            with open(d, "w") as f:
-                json.dump(line, f)
-            log(f"full bench record: {detail} ({len(json.dumps(line))} bytes)")
+            detail = write_detail(line, detail)
         sys.stdout.flush()
         os.write(out_fd, (json.dumps(headline(line, detail)) + "\n").encode())
     D.close()

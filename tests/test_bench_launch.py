@@ -16,7 +16,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 
 def _env(**kw):
-    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GB_BENCH_FULL")}
     e.update(kw)
     return e
 
@@ -100,14 +100,47 @@ def test_smem_keys_follow_the_batches():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_phmm_steps_only_and_dumps_their_outputs(tmp_path):
+    """Without --full: the headline's K timed steps and nothing that takes runs of its own, and
+    --dump-outputs writes what the timed path returned, bit for bit what a direct call returns."""
+    from genomicsbench_palisade_amd import gen, phmm, set_device
+    from genomicsbench_palisade_amd._tc import TestcaseArray
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batches", "4",
+                        "--dump-outputs", str(tmp_path / "out"), "--detail-out", str(tmp_path / "d.json")],
+                       capture_output=True, text=True, timeout=280, env=_env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, lines[:3]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("fmi", "chain", "bsw", "cpu_baseline"):
+        assert line[k] is None
+    assert "small" not in line and "shard_proxy" not in line
+    set_device(0)
+    phmm.init_pairhmm()
+    ta = TestcaseArray.from_batches(gen.phmm_dataset("large", 4, seed=1))
+    res, rf, rd, ud = phmm.compute_likelihoods_both(ta)
+    got = {k: np.load(tmp_path / "out" / f"phmm_{k}.npy") for k in ("log10", "raw_f32", "raw_f64", "used_double")}
+    assert got["log10"].dtype == np.float64 and got["raw_f32"].dtype == np.float32
+    assert got["raw_f64"].dtype == np.float64 and got["used_double"].dtype == np.float32
+    assert (got["log10"].view(np.uint64) == res.view(np.uint64)).all()
+    # raw f32: the value wherever it is used; a testcase that falls back may have left its f32 pass early (0)
+    same32 = got["raw_f32"].view(np.uint32) == rf.view(np.uint32)
+    assert (same32 | ((rf < phmm.MIN_ACCEPTED) & ((got["raw_f32"] == 0) | (rf == 0)))).all()
+    assert ((got["raw_f32"] < phmm.MIN_ACCEPTED) == ud.astype(bool)).all()
+    assert (got["raw_f64"].view(np.uint64) == rd.view(np.uint64)).all()
+    assert (got["used_double"] == ud).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("gpus", ["1", "2"])
 def test_stdout_is_one_json_line(gpus, tmp_path):
     """The driver reads one JSON line from stdout: at N=1 and under the self-launcher at N=2 (two
     ranks sharing the GPU, gloo connection messages and library banners included) nothing else may
     reach it."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", gpus, "--only", "phmm", "--batches", "8", "--no-small",
-                        "--no-e2e", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--shard-of", "0",
-                        "--detail-out", str(tmp_path / "d.json")],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", gpus, "--full", "--only", "phmm", "--batches", "8",
+                        "--no-small", "--no-e2e", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
+                        "--shard-of", "0", "--detail-out", str(tmp_path / "d.json")],
                        capture_output=True, text=True, timeout=280, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()

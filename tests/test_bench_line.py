@@ -78,6 +78,52 @@ def test_pmc_traffic_marks_other_code_stale(tmp_path, monkeypatch):
     assert r["traffic_stale"] is False
 
 
+def test_dump_outputs_keeps_f64_casts_the_rest_and_caps_the_size(tmp_path):
+    import numpy as np
+    n = 1000
+    arrays = {"a": np.arange(n, dtype=np.float64), "b": np.arange(n, dtype=np.float32),
+              "c": (np.arange(n) % 2).astype(np.uint8)}
+    r = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert r["units"] == n and r["bytes"] == 16 * n
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in arrays}
+    assert [got[k].dtype for k in "abc"] == [np.float64, np.float32, np.float32]
+    assert all((got[k] == arrays[k]).all() for k in arrays)
+    # over the budget: the same seeded sample of units in every array, the same on every call
+    for d in ("s1", "s2"):
+        r = bench.dump_outputs(str(tmp_path / d), arrays, max_bytes=1600)
+        assert r["units"] == 100 and r["of"] == n and r["bytes"] <= 1600
+    s1 = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in arrays}
+    s2 = {k: np.load(tmp_path / "s2" / (k + ".npy")) for k in arrays}
+    assert len(s1["a"]) == 100 and (np.diff(s1["a"]) > 0).all()
+    assert (s1["a"] == s1["b"]).all() and (s1["c"] == s1["a"] % 2).all()
+    assert all((s1[k] == s2[k]).all() for k in arrays)
+
+
+def test_detail_record_falls_back_when_its_folder_cannot_be_written(tmp_path, monkeypatch):
+    import tempfile
+    ok = tmp_path / "sub" / "d.json"
+    assert bench.write_detail({"a": 1}, str(ok)) == str(ok) and json.load(open(ok)) == {"a": 1}
+    # a folder that cannot be made (here: its parent is a file): the record goes to the temporary
+    # directory and the run keeps its result line
+    (tmp_path / "blocked").write_text("")
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))
+    (tmp_path / "tmp").mkdir()
+    got = bench.write_detail({"a": 2}, str(tmp_path / "blocked" / "out" / "d2.json"))
+    assert got == str(tmp_path / "tmp" / "d2.json") and json.load(open(got)) == {"a": 2}
+
+
+def test_legs_beyond_the_headline_need_full():
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("GB_BENCH_FULL", "WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--only", "fmi"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode != 0 and "need --full" in r.stderr and r.stdout == ""
+    # --full, or GB_BENCH_FULL=1 for a script's every call, lets the leg through (dry run: nothing starts)
+    for extra, e in ((["--full"], env), ([], dict(env, GB_BENCH_FULL="1"))):
+        r = subprocess.run(cmd + extra + ["--launch-dry-run"], capture_output=True, text=True, timeout=120, env=e)
+        assert r.returncode == 0 and "--only" in json.loads(r.stdout)["cmd"], r.stderr
+
+
 def test_source_digest_is_stable():
     assert bench.source_digest() == bench.source_digest()
     assert len(bench.source_digest()) == 16

@@ -10,7 +10,7 @@
 #   probe  one probe script per call: PROBE="tools/x.py args" -> gpurun_out/probe_TAG.log
 # Usage: gpu_checkpoint.sh TAG [stages...]   (default stages: tests smoke bench)
 #   gpurun --timeout 1200 -- 'bash tools/gpu_checkpoint.sh r04a tests smoke bench prof'
-# Environment: TESTS (pytest paths / -k, default "tests"), BENCH_ARGS (default "--steps 20 --warmup 5"),
+# Environment: TESTS (pytest paths / -k, default "tests"), BENCH_ARGS (default "--full --steps 20 --warmup 5"),
 #   PROBE (the probe stage's command line, run under python3)
 # Then, here: python tools/collect_checkpoint.py TAG  (copies the summaries into profiles/).
 set -o pipefail
@@ -20,7 +20,7 @@ export TMPDIR=/tmp
 TAG=${1:?tag}
 shift
 STAGES=${*:-tests smoke bench}
-BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5}
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}
 for s in $STAGES; do
   case $s in
     tests)

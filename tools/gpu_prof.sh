@@ -8,6 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-r01}
+export GB_BENCH_FULL=1  # bench.py --full for every run below (the legs beyond the plain phmm steps)
 LEGS="--only phmm,fmi,chain,bsw --no-cpu-baseline --no-small --no-e2e --shard-of 0"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG} -o run -- python3 bench.py --steps 5 --warmup 1 $LEGS > gpurun_out/prof_${TAG}.json 2> gpurun_out/prof_${TAG}.err || { echo "kernel-trace run failed"; tail -20 gpurun_out/prof_${TAG}.err; exit 1; }
 echo "kernel trace ok"
