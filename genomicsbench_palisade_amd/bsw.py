@@ -157,3 +157,85 @@ def get_scores8(pairs, params=None, w_match: int = 1):
     check(L.gb_bsw_get_scores8(ctypes.byref(params), w_match, _buf(sp), pairs.n, _buf(pairs.tgt), len(pairs.tgt),
                                _buf(pairs.qry), len(pairs.qry), None), "gb_bsw_get_scores8")
     return sp
+
+
+# ---- banded global alignment with CIGAR traceback (ksw_global2, tools/bwa/ksw.c:504-606) ----------
+
+# gb_bsw_gpair (include/gb_bsw.h), 48 bytes
+GPAIR_DTYPE = np.dtype([("idr", "<i8"), ("idq", "<i8"), ("len1", "<i4"), ("len2", "<i4"), ("w", "<i4"),
+                        ("score", "<i4"), ("n_cigar", "<i4"), ("nm", "<i4"), ("cigar_off", "<i8")])
+assert GPAIR_DTYPE.itemsize == 48
+GLOBAL_MAX_TLEN = 2047
+CIGAR_OPS = "MID"  # op codes 0, 1, 2 of ksw_global2's len << 4 | op
+
+
+def _decl_global():
+    L = _decl()
+    if getattr(L, "_bsw_global_decl", False):
+        return L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.gb_bsw_global.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.gb_bsw_global_band.argtypes = [vp, i32, i32, i32]
+    L.gb_bsw_global_timing.argtypes = [vp, vp]
+    L._bsw_global_decl = True
+    return L
+
+
+def gpairs(pairs, w):
+    """gb_bsw_gpair records for a BswPairs set; w is one band half-width or one per pair."""
+    gp = np.zeros(pairs.n, GPAIR_DTYPE)
+    gp["idr"], gp["idq"] = pairs.toff, pairs.qoff
+    gp["len1"], gp["len2"] = pairs.tlen, pairs.qlen
+    gp["w"] = w
+    for f in ("score", "n_cigar", "nm", "cigar_off"):
+        gp[f] = -1
+    return gp
+
+
+def global_align(pairs, w, params=None, want_cigar=True):
+    """ksw_global2 for every pair of a BswPairs set (h0 is ignored) with band half-width w (scalar or
+    per pair): (score, n_cigar, nm, cigar_off, cigar) as numpy arrays; pair p's operations are
+    cigar[cigar_off[p] : cigar_off[p] + n_cigar[p]], each len << 4 | op with M = 0, I = 1, D = 2.
+    want_cigar=False asks for scores only: n_cigar 0, nm -1, an empty cigar."""
+    params = params if params is not None else default_params()
+    gp = gpairs(pairs, w)
+    cap = int(pairs.tlen.astype(np.int64).sum() + pairs.qlen.astype(np.int64).sum()) if want_cigar else 0
+    cigar = np.zeros(max(cap, 1), np.uint32)
+    used = ctypes.c_int64(0)
+    check(_decl_global().gb_bsw_global(ctypes.byref(params), _buf(gp), pairs.n, _buf(pairs.tgt), len(pairs.tgt),
+                                       _buf(pairs.qry), len(pairs.qry), cigar.ctypes.data if want_cigar else None,
+                                       cap, ctypes.byref(used)), "gb_bsw_global")
+    return (gp["score"].copy(), gp["n_cigar"].copy(), gp["nm"].copy(), gp["cigar_off"].copy(),
+            cigar[:used.value].copy())
+
+
+def global_timing():
+    """(fill_ms, walk_ms): device time of this thread's last global_align, summed over its chunks."""
+    a, b = ctypes.c_float(), ctypes.c_float()
+    check(_decl_global().gb_bsw_global_timing(ctypes.byref(a), ctypes.byref(b)), "gb_bsw_global_timing")
+    return a.value, b.value
+
+
+def global_band(len2, len1, w_cap=100, params=None):
+    """bwa_gen_cigar2's band half-width (bwa.c:151-160) for a query of len2 against a target of len1;
+    w_cap is its w_ argument. Scalars give an int, arrays an int32 array."""
+    params = params if params is not None else default_params()
+    L = _decl_global()
+
+    def one(q, t):
+        w = L.gb_bsw_global_band(ctypes.byref(params), int(q), int(t), int(w_cap))
+        check(min(w, 0), "gb_bsw_global_band")
+        return w
+    if np.ndim(len2) == 0 and np.ndim(len1) == 0:
+        return one(len2, len1)
+    q, t = np.broadcast_arrays(np.asarray(len2), np.asarray(len1))
+    # the rule depends on (len2, len1) only: evaluate each distinct pair of lengths once
+    key = q.astype(np.int64) * 4096 + t.astype(np.int64)
+    uniq, inv = np.unique(key, return_inverse=True)
+    vals = np.array([one(k // 4096, k % 4096) for k in uniq.tolist()], np.int32)
+    return vals[inv].reshape(q.shape)
+
+
+def cigar_string(ops):
+    """'30M1D29M' for an array of len << 4 | op."""
+    return "".join(f"{int(o) >> 4}{CIGAR_OPS[int(o) & 15]}" for o in ops)

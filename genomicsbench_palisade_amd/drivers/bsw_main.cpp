@@ -8,6 +8,11 @@
 // 2048/256-byte strides; results are identical. -b is accepted; the GPU takes the whole set per call
 // (batching only distributed work over OpenMP threads in the reference). -o writes one line per
 // pair: score qle tle gtle gscore max_off.
+// -global runs the step that follows the extension in a bwa-mem-style caller instead: the banded
+// global alignment of each query against its target (gb_bsw_global == bwa's ksw_global2). The first
+// line of each pair record is then read as the band half-width w instead of h0, and one line per
+// pair, score NM CIGAR (tab separated), goes to the -o file, or to stdout when there is none (the
+// informational lines then go to stderr).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +25,14 @@
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
   const char *pair_file = nullptr, *out_file = nullptr;
-  for (int i = 1; i + 1 < argc; i += 2) {
+  bool global = false;
+  for (int i = 1; i < argc; i += 2) {
+    if (!strcmp(argv[i], "-global")) {  // the only flag without a value
+      global = true;
+      --i;
+      continue;
+    }
+    if (i + 1 >= argc) break;
     if (!strcmp(argv[i], "-match")) w_match = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-mismatch")) w_mismatch = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-ambig")) w_ambig = atoi(argv[i + 1]);
@@ -83,11 +95,60 @@ int main(int argc, char **argv) {
   }
   fclose(f);
   const double read_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
-  printf("Number of input pairs: %zu\n", pairs.size());
-  printf("Read time = %0.2lf s\n", read_s);
+  FILE *info = global && !out_file ? stderr : stdout;
+  fprintf(info, "Number of input pairs: %zu\n", pairs.size());
+  fprintf(info, "Read time = %0.2lf s\n", read_s);
 
   int8_t mat[25];
   gb_bsw_fill_scmat(w_match, w_mismatch, w_ambig, mat);
+  if (global) {
+    gb_bsw_params gp;
+    gb_bsw_default_params(&gp);
+    gp.o_del = gp.o_ins = w_open;
+    gp.e_del = gp.e_ins = w_extend;
+    memcpy(gp.mat, mat, sizeof(mat));
+    std::vector<gb_bsw_gpair> gpairs(pairs.size());
+    size_t cap = 0;
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      gb_bsw_gpair &g = gpairs[k];
+      memset(&g, 0, sizeof(g));
+      g.idr = pairs[k].idr;
+      g.idq = pairs[k].idq;
+      g.len1 = pairs[k].len1;
+      g.len2 = pairs[k].len2;
+      g.w = pairs[k].h0;  // the record's first line
+      cap += (size_t)g.len1 + (size_t)g.len2;
+    }
+    std::vector<uint32_t> cigar(cap ? cap : 1);
+    int64_t used = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int st = gb_bsw_global(&gp, gpairs.data(), (int64_t)gpairs.size(), ref.data(), (int64_t)ref.size(), qer.data(),
+                                 (int64_t)qer.size(), cigar.data(), (int64_t)cigar.size(), &used);
+    const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (st) {
+      fprintf(stderr, "gb_bsw_global failed (%d): %s\n", st, gb_last_error());
+      return 1;
+    }
+    fprintf(info, "Executed MI355X banded global alignment (gfx950)...\n");
+    fprintf(info, "Overall alignment time = %0.3f s (%lld CIGAR operations incl. host<->device copies)\n", sw_s,
+            (long long)used);
+    fprintf(info, "Total Pairs processed: %zu\n", pairs.size());
+    FILE *o = out_file ? fopen(out_file, "w") : stdout;
+    if (!o) {
+      fprintf(stderr, "Could not open file: %s\n", out_file);
+      return 1;
+    }
+    for (const auto &g : gpairs) {
+      fprintf(o, "%d\t%d\t", g.score, g.nm);
+      for (int32_t k = 0; k < g.n_cigar; ++k) {
+        const uint32_t op = cigar[(size_t)g.cigar_off + (size_t)k];
+        fprintf(o, "%u%c", op >> 4, "MID"[op & 3]);
+      }
+      fputc('\n', o);
+    }
+    if (out_file) fclose(o);
+    return 0;
+  }
   const int zdrop = 100, w = 100, end_bonus = 5;
   BandedPairWiseSW bsw(w_open, w_extend, w_open, w_extend, zdrop, end_bonus, mat, (int8_t)w_match,
                        (int8_t)w_mismatch, threads);

@@ -86,6 +86,48 @@ int gb_bsw_get_scores8(const gb_bsw_params *params, int32_t w_match, gb_seqpair 
                        const uint8_t *seq_buf_ref, int64_t ref_bytes, const uint8_t *seq_buf_qer,
                        int64_t qer_bytes, int64_t *total_cells);
 
+/* ---- banded global alignment with CIGAR traceback: bwa's ksw_global2 (tools/bwa/ksw.c:504-606),
+ * the step bwa_gen_cigar2 (tools/bwa/bwa.c:121-208) runs on a region getScores16 chose. Per pair:
+ * score, CIGAR (len << 4 | op, M = 0, I = 1, D = 2, as ksw_global2 returns it) and NM, each bit for
+ * bit what the reference computes. NM is bwa_gen_cigar2's count (bwa.c:169-200): mismatching
+ * positions inside M runs plus the lengths of the I runs and of the D runs that are neither the
+ * first nor the last operation (bwa.c:187 leaves those out).
+ *
+ * Accepted domain, per pair: 1 <= len2 <= GB_BSW_MAX_QLEN, 1 <= len1 <= GB_BSW_GLOBAL_MAX_TLEN,
+ * w >= |len1 - len2| (bwa_gen_cigar2 always passes at least |len1 - len2| + 3), offsets inside the
+ * sequence buffers; o_del, e_del, o_ins, e_ins in [0, 32768). Anything else fails the whole call
+ * with GB_ERR_ARG before any device work, nothing is written, and gb_last_error() names the pair.
+ * params->zdrop, end_bonus and w are ignored: the band is per pair. */
+#define GB_BSW_GLOBAL_MAX_TLEN 2047 /* the reference driver's target buffer (main_banded.cpp:59-62) */
+
+typedef struct gb_bsw_gpair { /* 48 bytes */
+  int64_t idr, idq;           /* target / query offsets, as in gb_seqpair */
+  int32_t len1, len2;         /* target, query length */
+  int32_t w;                  /* band half-width for this pair */
+  int32_t score, n_cigar, nm; /* out */
+  int64_t cigar_off;          /* out: index of this pair's first op in cigar[] */
+} gb_bsw_gpair;
+
+/* Operations are packed in pair order: pair p owns cigar[cigar_off .. cigar_off + n_cigar), and
+ * *cigar_used (may be NULL) receives their total. The sum of len1 + len2 over the pairs is always
+ * enough for cigar_cap. With cigar_cap smaller than the total the call returns GB_ERR_ARG, sets
+ * *cigar_used to the count required, fills the per-pair fields and leaves cigar[] untouched.
+ * cigar == NULL asks for scores only (no direction matrix, no walk): n_cigar = 0, nm = -1,
+ * cigar_off = 0, *cigar_used = 0. num_pairs == 0 succeeds. Device buffers are cached per (calling
+ * thread, device), as for gb_bsw_get_scores16. GB_ERR_STATE reports a traceback that did not end
+ * within len1 + len2 steps (an internal error; it cannot happen on a correct direction matrix). */
+int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t num_pairs,
+                  const uint8_t *seq_buf_ref, int64_t ref_bytes, const uint8_t *seq_buf_qer,
+                  int64_t qer_bytes, uint32_t *cigar, int64_t cigar_cap, int64_t *cigar_used);
+
+/* bwa_gen_cigar2's band rule (bwa.c:151-160) for a query of len2 against a target of len1; w_cap
+ * is its w_ argument. Needs e_del > 0 and e_ins > 0; GB_ERR_ARG (negative) otherwise. */
+int gb_bsw_global_band(const gb_bsw_params *params, int32_t len2, int32_t len1, int32_t w_cap);
+
+/* Device time of the calling thread's last gb_bsw_global on the current device, summed over its
+ * chunks: the DP fill kernel and the traceback kernel (0 for a scores-only call). */
+int gb_bsw_global_timing(float *fill_ms, float *walk_ms);
+
 #ifdef __cplusplus
 }
 #endif
