@@ -20,7 +20,7 @@ HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 .PHONY: all ref clean oracle
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
-     tests/_build/libdropin_bench.so tests/_build/liblds_poison.so
+     tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
 
 # the latency-bound DP loops schedule better for instruction-level parallelism (chain_rows -1.8 %,
 # phmm +0.8 %, bsw / fmi neutral; profiles/r04zb_sched_ab.log)
@@ -77,6 +77,11 @@ tests/_build/libdropin_bench.so: tests/cpp/dropin_bench.cpp $(LIB)/libgb_chain_d
 tests/_build/liblds_poison.so: tests/cpp/lds_poison.hip
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -shared -o $@ $<
+
+# stand-alone host program over gb::DevBuf / gb::PinnedBuf (tests/test_devbuf.py)
+tests/_build/devbuf_check: tests/cpp/devbuf_check.cpp $(LIB)/libgb.so $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall -o $@ $< -L$(LIB) -lgb -Wl,-rpath,'$$ORIGIN/../../$(LIB)'
 
 oracle:
 	$(MAKE) -s -C oracle all

@@ -562,8 +562,8 @@ struct gb_bsw_batch {
   // 16, 20; v = 5: wave-per-pair kernel), each segment sorted by decreasing target length
   static constexpr int kVariants = 6;
   int64_t seg[kVariants + 1] = {0};
-  uint32_t *d_order = nullptr;
-  unsigned long long *d_prof = nullptr;  // GB_BSW_PROF=1 per-variant sweep counters (development aid)
+  gb::DevBuf<uint32_t> d_order;
+  gb::DevBuf<unsigned long long> d_prof;  // GB_BSW_PROF=1 per-variant sweep counters (development aid)
   hipStream_t stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   // the variants' launches run side by side: each on its own stream, forked from and joined back
@@ -572,12 +572,12 @@ struct gb_bsw_batch {
   hipEvent_t fork = nullptr, join[kVariants] = {};
   gb_bsw_params params{};
   int64_t n = 0;
-  gbbsw::Pair *d_pairs = nullptr;
-  uint8_t *d_tgt = nullptr, *d_qry = nullptr;
-  int32_t *d_out6 = nullptr, *d_cells = nullptr;
-  unsigned long long *d_total = nullptr;  // [0] total cells, [1] work counter
+  // grow-only: cached workspaces are refilled
+  gb::DevBuf<gbbsw::Pair> d_pairs;
+  gb::DevBuf<uint8_t> d_tgt, d_qry;
+  gb::DevBuf<int32_t> d_out6, d_cells;
+  gb::DevBuf<unsigned long long> d_total;  // [0] total cells, [1] work counter
   static constexpr int kTotals = 2;
-  size_t cap_n = 0, cap_tgt = 0, cap_qry = 0;  // allocated capacities (cached workspaces are refilled)
   bool ran = false;
 };
 
@@ -607,9 +607,6 @@ int gb_bsw_batch_destroy(gb_bsw_batch *B) {
   if (!B) return GB_OK;
   if (B->device >= 0) (void)hipSetDevice(B->device);
   if (B->stream) (void)hipStreamSynchronize(B->stream);
-  for (void *p : {(void *)B->d_prof, (void *)B->d_order, (void *)B->d_pairs, (void *)B->d_tgt, (void *)B->d_qry, (void *)B->d_out6, (void *)B->d_cells,
-                  (void *)B->d_total})
-    (void)hipFree(p);
   for (auto &e : B->ev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : B->join)
@@ -638,25 +635,16 @@ int bsw_batch_new(gb_bsw_batch **out) {
   for (auto &ev : B->join)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&B->fork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc(&B->d_total, gb_bsw_batch::kTotals * sizeof(unsigned long long));
-  if (e != hipSuccess) {
+  int st = GB_ERR_HIP;
+  if (e == hipSuccess)
+    st = B->d_total.reserve(gb_bsw_batch::kTotals);
+  else
     gb::set_error("gb_bsw_batch_create: %s", hipGetErrorString(e));
+  if (st) {
     gb_bsw_batch_destroy(B);
-    return GB_ERR_HIP;
+    return st;
   }
   *out = B;
-  return GB_OK;
-}
-
-// grow-only device buffer
-template <typename T>
-int bsw_reserve(T **p, size_t &cap, size_t want) {
-  if (want <= cap) return GB_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  cap = 0;
-  GB_HIP(hipMalloc(p, want * sizeof(T)));
-  cap = want;
   return GB_OK;
 }
 
@@ -677,8 +665,8 @@ int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpai
   }
   // The sequence buffers (the bulk of the bytes) go up on a helper thread while this one builds
   // the launch plan; the helper is joined on every return path.
-  if ((st0 = bsw_reserve(&B->d_tgt, B->cap_tgt, (size_t)std::max<int64_t>(ref_bytes, 1)))) return st0;
-  if ((st0 = bsw_reserve(&B->d_qry, B->cap_qry, (size_t)std::max<int64_t>(qer_bytes, 1)))) return st0;
+  if ((st0 = B->d_tgt.reserve((size_t)std::max<int64_t>(ref_bytes, 1)))) return st0;
+  if ((st0 = B->d_qry.reserve((size_t)std::max<int64_t>(qer_bytes, 1)))) return st0;
   hipError_t up_err = hipSuccess;
   struct Joiner {
     std::thread t;
@@ -686,7 +674,7 @@ int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpai
       if (t.joinable()) t.join();
     }
   } up;
-  auto upload = [&, dev = B->device, dt = B->d_tgt, dq = B->d_qry] {
+  auto upload = [&, dev = B->device, dt = B->d_tgt.get(), dq = B->d_qry.get()] {
     up_err = hipSetDevice(dev);
     if (up_err == hipSuccess && ref_bytes) up_err = hipMemcpy(dt, ref, (size_t)ref_bytes, hipMemcpyHostToDevice);
     if (up_err == hipSuccess && qer_bytes) up_err = hipMemcpy(dq, qer, (size_t)qer_bytes, hipMemcpyHostToDevice);
@@ -839,17 +827,11 @@ int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpai
   B->n = n;
   B->ran = false;
   const size_t nn = (size_t)std::max<int64_t>(n, 1);
-  size_t cap_pairs = B->cap_n, cap_order = B->cap_n, cap_out = B->cap_n * 6, cap_cells = B->cap_n;
-  int st = bsw_reserve(&B->d_pairs, cap_pairs, nn);
-  if (!st) st = bsw_reserve(&B->d_order, cap_order, nn);
-  if (!st) st = bsw_reserve(&B->d_out6, cap_out, nn * 6);
-  if (!st) st = bsw_reserve(&B->d_cells, cap_cells, nn);
-  if (st) {
-    // one of the four shares cap_n and may now be freed or smaller: the next fill reallocates all
-    B->cap_n = 0;
-    return st;
-  }
-  B->cap_n = std::max(B->cap_n, nn);
+  int st = B->d_pairs.reserve(nn);
+  if (!st) st = B->d_order.reserve(nn);
+  if (!st) st = B->d_out6.reserve(nn * 6);
+  if (!st) st = B->d_cells.reserve(nn);
+  if (st) return st;
   if (n) GB_HIP(hipMemcpyAsync(B->d_order, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, B->stream));
   if (n) GB_HIP(hipMemcpyAsync(B->d_pairs, P.data(), (size_t)n * sizeof(gbbsw::Pair), hipMemcpyHostToDevice, B->stream));
   GB_HIP(hipStreamSynchronize(B->stream));  // the host vectors die on return
@@ -915,7 +897,7 @@ int gb_bsw_batch_run(gb_bsw_batch *B) {
     const char *pe = getenv("GB_BSW_PROF");
     const bool prof = pe && *pe == '1';
     if (prof) {
-      if (!B->d_prof) GB_HIP(hipMalloc(&B->d_prof, 25 * sizeof(unsigned long long)));
+      if (int st = B->d_prof.reserve(25)) return st;
       GB_HIP(hipMemsetAsync(B->d_prof, 0, 25 * sizeof(unsigned long long), B->stream));
     }
     // variant v launches on side stream v, forked from `stream` here and joined back below
@@ -1061,8 +1043,8 @@ constexpr int64_t kSmallCall = 16384;  // pairs; GB_BSW_SMALL overrides (0 = nev
 struct SmallWs {
   int device = -1, num_cus = 256;
   hipStream_t stream = nullptr;
-  uint8_t *h = nullptr, *d = nullptr;
-  size_t hcap = 0, dcap = 0;
+  gb::PinnedBuf<uint8_t> h;
+  gb::DevBuf<uint8_t> d;
 };
 
 int64_t small_call_limit() {
@@ -1119,23 +1101,12 @@ int small_group(SmallWs *W, const std::vector<SmallReq *> &g) {
   const size_t o_list = up16(sizeof(gbbsw::Pair) * (size_t)n), o_ctl = o_list + up16(4 * (size_t)n),
                o_tgt = o_ctl + 16, o_qry = o_tgt + up16((size_t)tb), up_bytes = o_qry + up16((size_t)qb),
                o_out = up_bytes, o_cells = o_out + up16(24 * (size_t)n), d_bytes = o_cells + up16(4 * (size_t)n);
-  if (std::max(up_bytes, d_bytes - o_out) > W->hcap) {
-    if (W->h) (void)hipHostFree(W->h);
-    W->h = nullptr;
-    W->hcap = 0;
-    const size_t want = std::max<size_t>(2 * std::max(up_bytes, d_bytes - o_out), 1 << 20);
-    GB_HIP(hipHostMalloc(&W->h, want, hipHostMallocDefault));
-    W->hcap = want;
-  }
-  if (d_bytes > W->dcap) {
-    (void)hipFree(W->d);
-    W->d = nullptr;
-    W->dcap = 0;
-    const size_t want = std::max<size_t>(2 * d_bytes, 1 << 20);
-    GB_HIP(hipMalloc(&W->d, want));
-    W->dcap = want;
-  }
-  uint8_t *h = W->h;
+  // both grow to twice the need, at least 1 MiB
+  const size_t h_bytes = std::max(up_bytes, d_bytes - o_out);
+  int st = W->h.reserve(h_bytes, std::max<size_t>(2 * h_bytes, 1 << 20));
+  if (!st) st = W->d.reserve(d_bytes, std::max<size_t>(2 * d_bytes, 1 << 20));
+  if (st) return st;
+  uint8_t *h = W->h, *d = W->d;
   auto *P = reinterpret_cast<gbbsw::Pair *>(h);
   auto *list = reinterpret_cast<uint32_t *>(h + o_list);
   int64_t to = 0, qo = 0, k = 0;
@@ -1150,17 +1121,17 @@ int small_group(SmallWs *W, const std::vector<SmallReq *> &g) {
       qo += sp.len2;
     }
   std::memset(h + o_ctl, 0, 16);
-  GB_HIP(hipMemcpyAsync(W->d, h, up_bytes, hipMemcpyHostToDevice, W->stream));
+  GB_HIP(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, W->stream));
   gbbsw::Args A;
-  A.pairs = reinterpret_cast<const gbbsw::Pair *>(W->d);
-  A.list = reinterpret_cast<const uint32_t *>(W->d + o_list);
+  A.pairs = reinterpret_cast<const gbbsw::Pair *>(d);
+  A.list = reinterpret_cast<const uint32_t *>(d + o_list);
   A.n = n;
-  A.tgt = W->d + o_tgt;
-  A.qry = W->d + o_qry;
-  A.out6 = reinterpret_cast<int32_t *>(W->d + o_out);
-  A.cells = reinterpret_cast<int32_t *>(W->d + o_cells);
-  A.total_cells = reinterpret_cast<unsigned long long *>(W->d + o_ctl);
-  A.next = reinterpret_cast<unsigned int *>(W->d + o_ctl + 8);
+  A.tgt = d + o_tgt;
+  A.qry = d + o_qry;
+  A.out6 = reinterpret_cast<int32_t *>(d + o_out);
+  A.cells = reinterpret_cast<int32_t *>(d + o_cells);
+  A.total_cells = reinterpret_cast<unsigned long long *>(d + o_ctl);
+  A.next = reinterpret_cast<unsigned int *>(d + o_ctl + 8);
   A.o_del = params->o_del;
   A.e_del = params->e_del;
   A.o_ins = params->o_ins;
@@ -1173,7 +1144,7 @@ int small_group(SmallWs *W, const std::vector<SmallReq *> &g) {
   hipLaunchKernelGGL(gbbsw::bsw_extend_kernel, dim3((unsigned)blocks), dim3(64 * gbbsw::kWavesPerBlock), 0, W->stream, A);
   GB_HIP(hipGetLastError());
   // out6 and the per-pair cell counts back in one copy (they are adjacent on the device)
-  GB_HIP(hipMemcpyAsync(h, W->d + o_out, d_bytes - o_out, hipMemcpyDeviceToHost, W->stream));
+  GB_HIP(hipMemcpyAsync(h, d + o_out, d_bytes - o_out, hipMemcpyDeviceToHost, W->stream));
   GB_HIP(hipStreamSynchronize(W->stream));
   const auto *r6 = reinterpret_cast<const int32_t *>(h);
   const auto *cells = reinterpret_cast<const int32_t *>(h + (o_cells - o_out));

@@ -310,18 +310,6 @@ __global__ __launch_bounds__(64) void bsw_global_walk_kernel(WalkArgs A) {
   o4[3] = (int32_t)base;
 }
 
-// grow-only device buffer
-template <typename T>
-int reserve(T **p, size_t &cap, size_t want) {
-  if (want <= cap) return GB_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  cap = 0;
-  GB_HIP(hipMalloc(p, want * sizeof(T)));
-  cap = want;
-  return GB_OK;
-}
-
 // Chunk bounds: a chunk's direction matrices take at most kDirWords 16-bit words (1 GiB) and its
 // operation pool, sized for the worst case sum of tlen + qlen, at most kPoolOps entries (256 MiB).
 // One pair needs at most 64 * 2047 words and 2302 operations, so a chunk always holds a pair.
@@ -338,13 +326,12 @@ struct Ws {  // one per (calling thread, device), never freed (see gb_bsw_get_sc
   int device = -1, num_cus = 256;
   hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  uint8_t *d_tgt = nullptr, *d_qry = nullptr;
-  Pair *d_pairs = nullptr;
-  int32_t *d_out4 = nullptr;
-  uint16_t *d_dir = nullptr;
-  uint32_t *d_pool = nullptr;
-  unsigned int *d_ctl = nullptr;  // [0] fill work counter, [1] pool operations used, [2] first clamped pair
-  size_t cap_tgt = 0, cap_qry = 0, cap_pairs = 0, cap_out4 = 0, cap_dir = 0, cap_pool = 0;
+  gb::DevBuf<uint8_t> d_tgt, d_qry;
+  gb::DevBuf<Pair> d_pairs;
+  gb::DevBuf<int32_t> d_out4;
+  gb::DevBuf<uint16_t> d_dir;
+  gb::DevBuf<uint32_t> d_pool;
+  gb::DevBuf<unsigned int> d_ctl;  // [0] fill work counter, [1] pool operations used, [2] first clamped pair
   float fill_ms = 0.f, walk_ms = 0.f;
 };
 
@@ -364,14 +351,17 @@ int get_ws(int dev, Ws **out) {
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
   for (auto &ev : W->ev)
     if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e == hipSuccess) e = hipMalloc(&W->d_ctl, 4 * sizeof(unsigned int));
-  if (e != hipSuccess) {
+  int st = GB_ERR_HIP;
+  if (e == hipSuccess)
+    st = W->d_ctl.reserve(4);
+  else
     gb::set_error("gb_bsw_global workspace: %s", hipGetErrorString(e));
+  if (st) {
     for (auto &ev : W->ev)
       if (ev) (void)hipEventDestroy(ev);
     if (W->stream) (void)hipStreamDestroy(W->stream);
     delete W;
-    return GB_ERR_HIP;
+    return st;
   }
   g_ws.push_back(W);
   *out = W;
@@ -449,8 +439,8 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
   Ws *W = nullptr;
   if ((st = get_ws(dev, &W))) return st;
   W->fill_ms = W->walk_ms = 0.f;
-  if ((st = reserve(&W->d_tgt, W->cap_tgt, (size_t)ref_bytes))) return st;
-  if ((st = reserve(&W->d_qry, W->cap_qry, (size_t)qer_bytes))) return st;
+  if ((st = W->d_tgt.reserve((size_t)ref_bytes))) return st;
+  if ((st = W->d_qry.reserve((size_t)qer_bytes))) return st;
   GB_HIP(hipMemcpyAsync(W->d_tgt, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, W->stream));
   GB_HIP(hipMemcpyAsync(W->d_qry, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, W->stream));
 
@@ -480,11 +470,11 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
       ++hi;
     }
     const int64_t m = hi - lo;
-    if ((st = reserve(&W->d_pairs, W->cap_pairs, (size_t)m))) return st;
-    if ((st = reserve(&W->d_out4, W->cap_out4, (size_t)m * 4))) return st;
+    if ((st = W->d_pairs.reserve((size_t)m))) return st;
+    if ((st = W->d_out4.reserve((size_t)m * 4))) return st;
     if (want) {
-      if ((st = reserve(&W->d_dir, W->cap_dir, (size_t)words))) return st;
-      if ((st = reserve(&W->d_pool, W->cap_pool, (size_t)ops))) return st;
+      if ((st = W->d_dir.reserve((size_t)words))) return st;
+      if ((st = W->d_pool.reserve((size_t)ops))) return st;
     }
     const unsigned int ctl0[4] = {0u, 0u, 0xFFFFFFFFu, 0u};
     GB_HIP(hipMemcpyAsync(W->d_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, W->stream));
@@ -495,7 +485,7 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
     F.tgt = W->d_tgt;
     F.qry = W->d_qry;
     F.out4 = W->d_out4;
-    F.dir = want ? W->d_dir : nullptr;
+    F.dir = want ? W->d_dir.get() : nullptr;
     F.next = W->d_ctl;
     F.o_del = params->o_del;
     F.e_del = params->e_del;

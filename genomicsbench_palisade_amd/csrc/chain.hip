@@ -455,24 +455,13 @@ int batch_fill(gb_chain_batch *B, int64_t ncalls, const int64_t *offsets, const 
   B->bt = nullptr;
   B->ran = false;
   const int64_t nc = std::max<int64_t>(ncalls, 1), nn = std::max<int64_t>(na, 1);
-  if (nc > B->cap_calls) {
-    for (void *q : {(void *)B->d_off, (void *)B->d_aq, (void *)B->d_par4}) (void)hipFree(q);
-    B->d_off = nullptr, B->d_aq = nullptr, B->d_par4 = nullptr;
-    B->cap_calls = 0;
-    GB_HIP(hipMalloc(&B->d_off, (size_t)(nc + 1) * sizeof(int64_t)));
-    GB_HIP(hipMalloc(&B->d_aq, (size_t)nc * sizeof(float)));
-    GB_HIP(hipMalloc(&B->d_par4, (size_t)nc * 4 * sizeof(int32_t)));
-    B->cap_calls = nc;
-  }
-  if (nn > B->cap_anchors) {
-    for (void *q : {(void *)B->d_x, (void *)B->d_y, (void *)B->d_out}) (void)hipFree(q);
-    B->d_x = nullptr, B->d_y = nullptr, B->d_out = nullptr;
-    B->cap_anchors = 0;
-    GB_HIP(hipMalloc(&B->d_x, (size_t)nn * sizeof(uint64_t)));
-    GB_HIP(hipMalloc(&B->d_y, (size_t)nn * sizeof(uint64_t)));
-    GB_HIP(hipMalloc(&B->d_out, (size_t)nn * 4 * sizeof(int32_t)));
-    B->cap_anchors = nn;
-  }
+  int st = B->d_off.reserve((size_t)nc + 1);
+  if (!st) st = B->d_aq.reserve((size_t)nc);
+  if (!st) st = B->d_par4.reserve((size_t)nc * 4);
+  if (!st) st = B->d_x.reserve((size_t)nn);
+  if (!st) st = B->d_y.reserve((size_t)nn);
+  if (!st) st = B->d_out.reserve((size_t)nn * 4);
+  if (st) return st;
   B->ncalls = ncalls;
   B->nanchors = na;
   GB_HIP(hipMemcpy(B->d_off, offsets, (size_t)(ncalls + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -487,7 +476,7 @@ int batch_fill(gb_chain_batch *B, int64_t ncalls, const int64_t *offsets, const 
     GB_HIP(hipMemcpyAsync(B->d_y, y, (size_t)na * 8, hipMemcpyHostToDevice, B->stream));
   }
   // the block table: whole calls, or long calls as speculative segments (chain_split.hip)
-  const int st = gbchain::split_plan(B, offsets, x, params4);
+  st = gbchain::split_plan(B, offsets, x, params4);
   GB_HIP(hipStreamSynchronize(B->stream));  // the caller may free x / y on return
   return st;
 }
@@ -590,11 +579,14 @@ int batch_new(gb_chain_batch **out) {
   for (auto &ev : B->fj)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&B->fail_ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc(&B->d_vis, sizeof(unsigned long long));
-  if (e != hipSuccess) {
+  int st = GB_ERR_HIP;
+  if (e == hipSuccess)
+    st = B->d_vis.reserve(1);
+  else
     gb::set_error("gb_chain: %s", hipGetErrorString(e));
+  if (st) {
     gb_chain_batch_destroy(B);
-    return GB_ERR_HIP;
+    return st;
   }
   *out = B;
   return GB_OK;
@@ -636,7 +628,7 @@ int gb_chain_batch_run(gb_chain_batch *B) {
     const char *pe = getenv("GB_CHAIN_PROF");
     const int prof = (pe && (*pe == '1' || *pe == '2')) ? *pe - '0' : 0;
     if (prof) {
-      if (!B->d_prof) GB_HIP(hipMalloc(&B->d_prof, 16 * sizeof(unsigned long long)));
+      if (int st = B->d_prof.reserve(16)) return st;
       GB_HIP(hipMemsetAsync(B->d_prof, 0, 16 * sizeof(unsigned long long), B->stream));
       GB_HIP(hipMemsetAsync(B->d_prof + 8, 0xff, sizeof(unsigned long long), B->stream));
     }
@@ -704,16 +696,11 @@ int gb_chain_batch_destroy(gb_chain_batch *B) {
   if (!B) return GB_OK;
   if (B->stream) (void)hipStreamSynchronize(B->stream);
   gbchain::chain_bt_destroy(B->bt);
-  gbchain::split_free(B);
-  for (void *p : {(void *)B->d_off, (void *)B->d_aq, (void *)B->d_par4, (void *)B->d_x,
-                  (void *)B->d_y, (void *)B->d_out, (void *)B->d_vis, (void *)B->d_prof})
-    (void)hipFree(p);
   for (auto ev : B->ev)
     if (ev) (void)hipEventDestroy(ev);
   for (auto ev : B->fj)
     if (ev) (void)hipEventDestroy(ev);
   if (B->fail_ev) (void)hipEventDestroy(B->fail_ev);
-  if (B->h_fail) (void)hipHostFree(B->h_fail);
   if (B->stream2) (void)hipStreamDestroy(B->stream2);
   if (B->stream) (void)hipStreamDestroy(B->stream);
   delete B;

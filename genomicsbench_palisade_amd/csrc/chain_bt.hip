@@ -550,15 +550,12 @@ __global__ void k_copy(int32_t cap, int ncalls, const int32_t *__restrict__ eoff
 struct ChainBt {
   int64_t n = 0;  // anchors the buffers are sized for
   int ncalls = 0;
-  int32_t *cid = nullptr, *ecnt = nullptr, *eoff = nullptr, *nsel = nullptr, *rank = nullptr, *first = nullptr;
-  int32_t *ecall = nullptr, *clen = nullptr, *ctop = nullptr, *acc = nullptr, *alen = nullptr, *kidx = nullptr;
-  int32_t *aoff = nullptr, *kentry = nullptr, *ctr = nullptr, *bidx = nullptr, *bchain = nullptr;
-  int32_t *newoff = nullptr, *scratch = nullptr;
-  uint8_t *child = nullptr, *flag = nullptr, *own = nullptr;
-  uint64_t *key = nullptr, *ekeys = nullptr, *skeys = nullptr, *u = nullptr, *uout = nullptr;
-  uint64_t *ox = nullptr, *oy = nullptr;
-  W128 *w = nullptr;
-  void *temp = nullptr;
+  gb::DevBuf<int32_t> cid, ecnt, eoff, nsel, rank, first, ecall, clen, ctop, acc, alen, kidx, aoff, kentry, ctr, bidx,
+      bchain, newoff, scratch;
+  gb::DevBuf<uint8_t> child, flag, own;
+  gb::DevBuf<uint64_t> key, ekeys, skeys, u, uout, ox, oy;
+  gb::DevBuf<W128> w;
+  gb::DevBuf<uint8_t> temp;
   size_t temp_bytes = 0;
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool ran = false;
@@ -566,13 +563,6 @@ struct ChainBt {
 
 void chain_bt_destroy(ChainBt *T) {
   if (!T) return;
-  for (void *p : {(void *)T->cid, (void *)T->ecnt, (void *)T->eoff, (void *)T->nsel, (void *)T->rank,
-                  (void *)T->first, (void *)T->ecall, (void *)T->clen, (void *)T->ctop, (void *)T->acc,
-                  (void *)T->alen, (void *)T->kidx, (void *)T->aoff, (void *)T->kentry, (void *)T->ctr,
-                  (void *)T->bidx, (void *)T->bchain, (void *)T->newoff, (void *)T->scratch, (void *)T->child,
-                  (void *)T->flag, (void *)T->own, (void *)T->key, (void *)T->ekeys, (void *)T->skeys,
-                  (void *)T->u, (void *)T->uout, (void *)T->ox, (void *)T->oy, (void *)T->w, T->temp})
-    if (p) (void)hipFree(p);
   for (auto e : T->ev)
     if (e) (void)hipEventDestroy(e);
   delete T;
@@ -590,33 +580,35 @@ int bt_alloc(gb_chain_batch *B) {
   T->ncalls = (int)B->ncalls;
   const size_t nc1 = (size_t)B->ncalls + 1;
   for (auto &e : T->ev) GB_HIP(hipEventCreate(&e));
-  GB_HIP(hipMalloc(&T->cid, n * 4));
-  GB_HIP(hipMalloc(&T->ecnt, nc1 * 4));
-  GB_HIP(hipMalloc(&T->eoff, nc1 * 4));
-  GB_HIP(hipMalloc(&T->nsel, 4));
-  for (int32_t **p : {&T->rank, &T->first, &T->ecall, &T->clen, &T->ctop, &T->kentry, &T->ctr, &T->newoff})
-    GB_HIP(hipMalloc(p, n * 4));
-  for (int32_t **p : {&T->acc, &T->alen, &T->kidx, &T->aoff}) GB_HIP(hipMalloc(p, (n + 1) * 4));
-  GB_HIP(hipMalloc(&T->bidx, 2 * n * 4));
-  GB_HIP(hipMalloc(&T->bchain, 2 * n * 4));
-  GB_HIP(hipMalloc(&T->scratch, nc1 * kRsLevels * 512 * 4));  // bucket tables of the > kLdsW reorders
-  GB_HIP(hipMalloc(&T->child, n));
-  GB_HIP(hipMalloc(&T->flag, n));
-  GB_HIP(hipMalloc(&T->own, n));
-  for (uint64_t **p : {&T->key, &T->ekeys, &T->skeys, &T->u, &T->uout}) GB_HIP(hipMalloc(p, n * 8));
-  GB_HIP(hipMalloc(&T->ox, 2 * n * 8));
-  GB_HIP(hipMalloc(&T->oy, 2 * n * 8));
-  GB_HIP(hipMalloc(&T->w, n * sizeof(W128)));
+  const size_t nn = (size_t)n;
+  int st = T->ecnt.reserve(nc1);
+  if (!st) st = T->eoff.reserve(nc1);
+  if (!st) st = T->nsel.reserve(1);
+  for (auto *p : {&T->cid, &T->rank, &T->first, &T->ecall, &T->clen, &T->ctop, &T->kentry, &T->ctr, &T->newoff})
+    if (!st) st = p->reserve(nn);
+  for (auto *p : {&T->acc, &T->alen, &T->kidx, &T->aoff})
+    if (!st) st = p->reserve(nn + 1);
+  for (auto *p : {&T->bidx, &T->bchain})
+    if (!st) st = p->reserve(2 * nn);
+  if (!st) st = T->scratch.reserve(nc1 * kRsLevels * 512);  // bucket tables of the > kLdsW reorders
+  for (auto *p : {&T->child, &T->flag, &T->own})
+    if (!st) st = p->reserve(nn);
+  for (auto *p : {&T->key, &T->ekeys, &T->skeys, &T->u, &T->uout})
+    if (!st) st = p->reserve(nn);
+  for (auto *p : {&T->ox, &T->oy})
+    if (!st) st = p->reserve(2 * nn);
+  if (!st) st = T->w.reserve(nn);
+  if (st) return st;
   // hipCUB temporary storage: the largest of the select, the segmented sort and the scans
   size_t a = 0, b = 0, c = 0, d = 0;
-  GB_HIP(hipcub::DeviceSelect::Flagged(nullptr, a, T->key, T->flag, T->ekeys, T->nsel, (int)n));
-  GB_HIP(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, b, T->ekeys, T->skeys, (int)n, T->ncalls,
-                                                               T->eoff, T->eoff + 1));
-  GB_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, c, T->acc, T->kidx, (int)n + 1));
-  GB_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, d, T->ecnt, T->eoff, T->ncalls + 1));
+  GB_HIP(hipcub::DeviceSelect::Flagged(nullptr, a, T->key.get(), T->flag.get(), T->ekeys.get(), T->nsel.get(),
+                                       (int)n));
+  GB_HIP(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, b, T->ekeys.get(), T->skeys.get(), (int)n,
+                                                               T->ncalls, T->eoff.get(), T->eoff + 1));
+  GB_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, c, T->acc.get(), T->kidx.get(), (int)n + 1));
+  GB_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, d, T->ecnt.get(), T->eoff.get(), T->ncalls + 1));
   T->temp_bytes = std::max(std::max(a, b), std::max(c, d));
-  GB_HIP(hipMalloc(&T->temp, std::max<size_t>(T->temp_bytes, 16)));
-  return GB_OK;
+  return T->temp.reserve(std::max<size_t>(T->temp_bytes, 16));
 }
 
 }  // namespace
@@ -648,12 +640,13 @@ int gb_chain_batch_backtrack(gb_chain_batch *B, int32_t min_cnt, int32_t min_sc)
                        T->flag, T->ecnt);
     GB_HIP(hipGetLastError());
     size_t tb = T->temp_bytes;
-    GB_HIP(hipcub::DeviceSelect::Flagged(T->temp, tb, T->key, T->flag, T->ekeys, T->nsel, (int)n, s));
+    GB_HIP(hipcub::DeviceSelect::Flagged(T->temp, tb, T->key.get(), T->flag.get(), T->ekeys.get(), T->nsel.get(),
+                                         (int)n, s));
     tb = T->temp_bytes;
-    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->ecnt, T->eoff, nc + 1, s));
+    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->ecnt.get(), T->eoff.get(), nc + 1, s));
     tb = T->temp_bytes;
-    GB_HIP(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(T->temp, tb, T->ekeys, T->skeys, (int)n, nc, T->eoff,
-                                                                 T->eoff + 1, 0, 64, s));
+    GB_HIP(hipcub::DeviceSegmentedRadixSort::SortKeysDescending(T->temp, tb, T->ekeys.get(), T->skeys.get(), (int)n, nc,
+                                                                 T->eoff.get(), T->eoff + 1, 0, 64, s));
     // starts' ranks, subtree minima, chain lengths/tops
     GB_HIP(hipMemsetAsync(T->rank, 0x7f, n * 4, s));  // 0x7f7f7f7f > any rank; normalised below
     hipLaunchKernelGGL(k_rank, dim3(ga), dim3(256), 0, s, cap, T->eoff, nc, B->d_off, T->skeys, T->ecall, T->rank);
@@ -668,9 +661,9 @@ int gb_chain_batch_backtrack(gb_chain_batch *B, int32_t min_cnt, int32_t min_sc)
                        T->first, T->clen, T->ctop, min_cnt, min_sc, T->u, T->acc, T->alen, T->own);
     GB_HIP(hipGetLastError());
     tb = T->temp_bytes;
-    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->acc, T->kidx, (int)n + 1, s));
+    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->acc.get(), T->kidx.get(), (int)n + 1, s));
     tb = T->temp_bytes;
-    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->alen, T->aoff, (int)n + 1, s));
+    GB_HIP(hipcub::DeviceScan::ExclusiveSum(T->temp, tb, T->alen.get(), T->aoff.get(), (int)n + 1, s));
     hipLaunchKernelGGL(k_special, dim3(ga), dim3(256), 0, s, cap, T->eoff, nc, B->d_off, T->ecall, T->skeys, T->acc,
                        T->own, T->kidx, T->aoff, T->bidx, T->bchain, T->kentry);
     GB_HIP(hipMemsetAsync(T->ctr, 0, n * 4, s));

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "gb_common.h"
+
 namespace gbchain {
 struct ChainBt;                   // chain_bt.hip
 void chain_bt_destroy(ChainBt *);
@@ -48,14 +50,14 @@ struct gb_chain_batch {
   hipStream_t stream2 = nullptr;            // full-ring blocks run here, beside the small-ring ones
   hipEvent_t fj[2] = {nullptr, nullptr};    // fork / join of the two streams
   int64_t ncalls = 0, nanchors = 0;
-  int64_t cap_calls = 0, cap_anchors = 0;  // allocated sizes (a refilled batch reuses its buffers)
-  int64_t *d_off = nullptr;
-  float *d_aq = nullptr;
-  int32_t *d_par4 = nullptr;
-  uint64_t *d_x = nullptr, *d_y = nullptr;
-  int32_t *d_out = nullptr;  // score | parent | target | peak, nanchors (>= 1) each
-  unsigned long long *d_vis = nullptr;
-  unsigned long long *d_prof = nullptr;  // GB_CHAIN_PROF=1 phase clocks (development aid)
+  // grow-only: a refilled batch reuses its buffers
+  gb::DevBuf<int64_t> d_off;
+  gb::DevBuf<float> d_aq;
+  gb::DevBuf<int32_t> d_par4;
+  gb::DevBuf<uint64_t> d_x, d_y;
+  gb::DevBuf<int32_t> d_out;  // score | parent | target | peak, nanchors (>= 1) each
+  gb::DevBuf<unsigned long long> d_vis;
+  gb::DevBuf<unsigned long long> d_prof;  // GB_CHAIN_PROF=1 phase clocks (development aid)
   bool ran = false;
   gbchain::ChainBt *bt = nullptr;  // backtrack state (gb_chain_batch_backtrack)
 
@@ -64,8 +66,7 @@ struct gb_chain_batch {
   std::vector<gbchain::VCall> vc;
   int n_rows = 0;
   int n_small = 0;
-  gbchain::VCall *d_vc = nullptr;
-  int64_t cap_vc = 0;
+  gb::DevBuf<gbchain::VCall> d_vc;
   // long calls as speculative segments (chain_split.hip); empty when no call is split
   std::vector<gbchain::SplitCall> split;
   std::vector<gbchain::Seg> segs;
@@ -73,25 +74,22 @@ struct gb_chain_batch {
   std::vector<int32_t> st;  // window start st(i) of the split calls' anchors >= c1, chunk-space index
   int64_t scratch_n = 0;
   int max_split_n = 0;
-  gbchain::SplitCall *d_split = nullptr;
-  gbchain::Seg *d_segs = nullptr;
-  gbchain::Chunk *d_chunks = nullptr;
-  int32_t *d_st = nullptr;        // st, chunk-space index
-  int32_t *d_sscore = nullptr, *d_sparent = nullptr;  // segment scratch
-  int32_t *d_smark = nullptr;     // segment scratch: targets marks of chain_rows' speculative blocks
-  uint64_t *d_need = nullptr;     // per chunk: anchors verify_lanes leaves to verify_kernel
-  int32_t *d_slow = nullptr;      // [0]: chunks with such anchors, then their indices (verify_kernel's work list)
-  int32_t *d_front = nullptr;     // per split call: first anchor not known to be final
-  int32_t *d_fail = nullptr;      // per split call: first anchor whose guess failed verification
-  int32_t *d_link[2] = {nullptr, nullptr};  // pointer jumping (chunk-space index or -1)
-  int32_t *d_val[2] = {nullptr, nullptr};
-  int32_t *d_t2 = nullptr;                 // split anchors' targets marks, merged at the end
-  unsigned long long *d_viscall = nullptr; // visited pairs per split call
-  int64_t cap_split = 0, cap_segs = 0, cap_chunks = 0, cap_st = 0, cap_sscore = 0, cap_sparent = 0, cap_smark = 0, cap_need = 0, cap_slow = 0, cap_front = 0,
-          cap_jump = 0, cap_t2 = 0, cap_viscall = 0;
+  gb::DevBuf<gbchain::SplitCall> d_split;
+  gb::DevBuf<gbchain::Seg> d_segs;
+  gb::DevBuf<gbchain::Chunk> d_chunks;
+  gb::DevBuf<int32_t> d_st;        // st, chunk-space index
+  gb::DevBuf<int32_t> d_sscore, d_sparent;  // segment scratch
+  gb::DevBuf<int32_t> d_smark;     // segment scratch: targets marks of chain_rows' speculative blocks
+  gb::DevBuf<uint64_t> d_need;     // per chunk: anchors verify_lanes leaves to verify_kernel
+  gb::DevBuf<int32_t> d_slow;      // [0]: chunks with such anchors, then their indices (verify_kernel's work list)
+  gb::DevBuf<int32_t> d_front;     // per split call: first anchor not known to be final, then d_fail's entries
+  int32_t *d_fail = nullptr;       // per split call: first anchor whose guess failed verification (in d_front)
+  gb::DevBuf<int32_t> d_link[2];   // pointer jumping (chunk-space index or -1)
+  gb::DevBuf<int32_t> d_val[2];
+  gb::DevBuf<int32_t> d_t2;                 // split anchors' targets marks, merged at the end
+  gb::DevBuf<unsigned long long> d_viscall; // visited pairs per split call
   int64_t spec_rounds = 0, fixups = 0;  // statistics of the last run
-  int32_t *h_fail = nullptr;   // pinned copy of d_fail (the host reads it mid-step)
-  int64_t cap_hfail = 0;
+  gb::PinnedBuf<int32_t> h_fail;  // pinned copy of d_fail (the host reads it mid-step)
   hipEvent_t fail_ev = nullptr;  // recorded behind the d_fail copy
 };
 
@@ -100,7 +98,6 @@ namespace gbchain {
 int split_plan(gb_chain_batch *B, const int64_t *offsets, const uint64_t *x, const int32_t *params4);
 int split_resolve(gb_chain_batch *B);
 int step_clear_launch(gb_chain_batch *B);  // every per-step clear in one launch (before the blocks)
-void split_free(gb_chain_batch *B);
 int launch_chain(gb_chain_batch *B, const VCall *d_vc, int nvc, int prof, bool small, hipStream_t stream);
 int launch_table(gb_chain_batch *B, int prof);
 // chain_rows.hip

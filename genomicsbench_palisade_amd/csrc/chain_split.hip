@@ -535,17 +535,7 @@ __global__ __launch_bounds__(256) void merge_targets(SplitArgs A) {
 
 namespace {
 
-template <typename T>
-int grow(T **p, int64_t *cap, int64_t need) {
-  need = std::max<int64_t>(need, 1);
-  if (need <= *cap) return GB_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  GB_HIP(hipMalloc(p, (size_t)need * sizeof(T)));
-  *cap = need;
-  return GB_OK;
-}
+size_t at_least_1(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
 
 // Segment length: as long as the segment's sequential run (its window and warm-up included) stays
 // under the batch's throughput time, so small batches get shorter segments; shorter ones cost more
@@ -807,40 +797,28 @@ int split_plan(gb_chain_batch *B, const int64_t *offsets, const uint64_t *x, con
   }
   const int64_t nvc = (int64_t)B->vc.size();
   // room for one fix-up block per split call behind the table (split_resolve)
-  if (int st = grow(&B->d_vc, &B->cap_vc, nvc + (int64_t)B->split.size())) return st;
+  if (int st = B->d_vc.reserve(at_least_1(nvc + (int64_t)B->split.size()))) return st;
   if (nvc) GB_HIP(hipMemcpy(B->d_vc, B->vc.data(), (size_t)nvc * sizeof(VCall), hipMemcpyHostToDevice));
   if (B->split.empty()) return GB_OK;
   const int64_t ns = (int64_t)B->split.size(), nch = (int64_t)B->chunks.size();
-  int st = grow(&B->d_split, &B->cap_split, ns);
-  if (!st) st = grow(&B->d_segs, &B->cap_segs, (int64_t)B->segs.size());
-  if (!st) st = grow(&B->d_chunks, &B->cap_chunks, nch);
-  if (!st) st = grow(&B->d_st, &B->cap_st, 64 * nch);
-  if (!st) st = grow(&B->d_sscore, &B->cap_sscore, B->scratch_n);
-  if (!st) st = grow(&B->d_sparent, &B->cap_sparent, B->scratch_n);
-  if (!st) st = grow(&B->d_smark, &B->cap_smark, B->scratch_n);
-  if (!st) st = grow(&B->d_front, &B->cap_front, 2 * ns);
-  if (!st) st = grow(&B->d_viscall, &B->cap_viscall, ns);
-  if (!st) st = grow(&B->d_t2, &B->cap_t2, B->nanchors);
-  if (!st) st = grow(&B->d_need, &B->cap_need, nch);
-  if (!st) st = grow(&B->d_slow, &B->cap_slow, nch + 1);
+  int st = B->d_split.reserve(at_least_1(ns));
+  if (!st) st = B->d_segs.reserve(at_least_1((int64_t)B->segs.size()));
+  if (!st) st = B->d_chunks.reserve(at_least_1(nch));
+  if (!st) st = B->d_st.reserve(at_least_1(64 * nch));
+  if (!st) st = B->d_sscore.reserve(at_least_1(B->scratch_n));
+  if (!st) st = B->d_sparent.reserve(at_least_1(B->scratch_n));
+  if (!st) st = B->d_smark.reserve(at_least_1(B->scratch_n));
+  if (!st) st = B->d_front.reserve(at_least_1(2 * ns));
+  if (!st) st = B->d_viscall.reserve(at_least_1(ns));
+  if (!st) st = B->d_t2.reserve(at_least_1(B->nanchors));
+  if (!st) st = B->d_need.reserve(at_least_1(nch));
+  if (!st) st = B->d_slow.reserve(at_least_1(nch + 1));
+  for (int k = 0; k < 2; k++) {
+    if (!st) st = B->d_link[k].reserve((size_t)64 * nch);
+    if (!st) st = B->d_val[k].reserve((size_t)64 * nch);
+  }
   if (st) return st;
   B->d_fail = B->d_front + ns;
-  {
-    const int64_t need = 64 * nch;
-    if (need > B->cap_jump) {
-      for (int k = 0; k < 2; k++) {
-        (void)hipFree(B->d_link[k]);
-        (void)hipFree(B->d_val[k]);
-        B->d_link[k] = B->d_val[k] = nullptr;
-      }
-      B->cap_jump = 0;
-      for (int k = 0; k < 2; k++) {
-        GB_HIP(hipMalloc(&B->d_link[k], (size_t)need * sizeof(int32_t)));
-        GB_HIP(hipMalloc(&B->d_val[k], (size_t)need * sizeof(int32_t)));
-      }
-      B->cap_jump = need;
-    }
-  }
   GB_HIP(hipMemcpy(B->d_split, B->split.data(), (size_t)ns * sizeof(SplitCall), hipMemcpyHostToDevice));
   GB_HIP(hipMemcpy(B->d_segs, B->segs.data(), B->segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
   GB_HIP(hipMemcpy(B->d_chunks, B->chunks.data(), (size_t)nch * sizeof(Chunk), hipMemcpyHostToDevice));
@@ -864,13 +842,7 @@ int split_resolve(gb_chain_batch *B) {
   const int64_t ns = (int64_t)B->split.size();
   const unsigned nch = (unsigned)B->chunks.size();
   std::vector<int32_t> front((size_t)ns);
-  if (ns > B->cap_hfail) {
-    if (B->h_fail) (void)hipHostFree(B->h_fail);
-    B->h_fail = nullptr;
-    B->cap_hfail = 0;
-    GB_HIP(hipHostMalloc((void **)&B->h_fail, (size_t)ns * sizeof(int32_t), hipHostMallocDefault));
-    B->cap_hfail = ns;
-  }
+  if (int st = B->h_fail.reserve((size_t)ns)) return st;
   const int32_t *fail = B->h_fail;
   // front = c1, t2, viscall, fail and the work-list count were cleared by step_clear at the step's start
   for (int64_t k = 0; k < ns; k++) front[(size_t)k] = B->split[(size_t)k].c1;
@@ -967,15 +939,6 @@ int split_resolve(gb_chain_batch *B) {
   hipLaunchKernelGGL(merge_targets, dim3((unsigned)ns), dim3(256), 0, B->stream, A);
   GB_HIP(hipGetLastError());
   return GB_OK;
-}
-
-void split_free(gb_chain_batch *B) {
-  for (void *p : {(void *)B->d_vc, (void *)B->d_split, (void *)B->d_segs, (void *)B->d_chunks, (void *)B->d_st,
-                  (void *)B->d_sscore, (void *)B->d_sparent, (void *)B->d_front, (void *)B->d_link[0],
-                  (void *)B->d_link[1], (void *)B->d_val[0], (void *)B->d_val[1], (void *)B->d_t2,
-                  (void *)B->d_viscall, (void *)B->d_smark, (void *)B->d_need, (void *)B->d_slow})
-    (void)hipFree(p);
-  B->d_vc = nullptr;
 }
 
 }  // namespace gbchain

@@ -999,41 +999,36 @@ struct gb_fmi_reads {
   int32_t nreads = 0, stride = 0;
   int lanes = 0;  // resident lanes of the persistent search grid
   int cus = 256;
-  uint8_t *d_qdb = nullptr;
-  uint32_t *d_q4 = nullptr;
+  // grow-only buffers: a destroyed read set goes back to its thread's free list with its stream and
+  // buffers, and the next create reuses them (no allocation or free per batch)
+  gb::DevBuf<uint8_t> d_qdb;
+  gb::DevBuf<uint32_t> d_q4;
   int32_t q4_stride = 0;
-  uint32_t *d_q2 = nullptr;    // 2-bit codes (smem_search<2, ...>)
+  gb::DevBuf<uint32_t> d_q2;    // 2-bit codes (smem_search<2, ...>)
   int32_t q2_stride = 0;
-  uint32_t *d_npos = nullptr;  // per read: N positions
-  int32_t *d_lens = nullptr;
-  gbfmi::PEnt *d_scratch = nullptr;
-  gb_smem *d_slots = nullptr;
-  int32_t *d_counts = nullptr;
-  int32_t *d_phase = nullptr;
-  int64_t *d_offsets = nullptr;
-  gb_smem *d_out = nullptr;
-  int64_t out_cap = 0;
-  int32_t *d_ctl = nullptr;  // [0] next_read, [1] overflow count, [2] fatal, [3] unused, [4] heavy reads
-  int32_t *d_heavy = nullptr;  // reads handed to smem_heavy (capacity nreads)
-  int32_t *d_ovf_list = nullptr;
-  int32_t *d_ovf_pos = nullptr;
-  gb_smem *d_big = nullptr;
-  unsigned long long *d_calls = nullptr;
-  void *d_temp = nullptr;
+  gb::DevBuf<uint32_t> d_npos;  // per read: N positions
+  gb::DevBuf<int32_t> d_lens;
+  gb::DevBuf<gbfmi::PEnt> d_scratch;
+  gb::DevBuf<gb_smem> d_slots;
+  gb::DevBuf<int32_t> d_counts;
+  gb::DevBuf<int32_t> d_phase;
+  gb::DevBuf<int64_t> d_offsets;
+  gb::DevBuf<gb_smem> d_out;
+  gb::DevBuf<int32_t> d_ctl;  // [0] next_read, [1] overflow count, [2] fatal, [3] unused, [4] heavy reads
+  gb::DevBuf<int32_t> d_heavy;  // reads handed to smem_heavy (capacity nreads)
+  gb::DevBuf<int32_t> d_ovf_list;
+  gb::DevBuf<int32_t> d_ovf_pos;
+  gb::DevBuf<gb_smem> d_big;
+  gb::DevBuf<unsigned long long> d_calls;
+  gb::DevBuf<uint8_t> d_temp;
   size_t temp_bytes = 0;
   bool ran = false;
   bool complete = false;   // every buffer allocated: only such a read set is recycled on destroy
   bool scattered = false;  // d_out holds the last search's compacted SMEMs
   int64_t total = 0;
   gbfmi::SaJob *sa = nullptr;
-  int64_t *d_trace = nullptr;  // GB_FMI_FLAGS & 8 diagnostic (3 x nreads), allocated on demand
-  size_t cap_trace = 0;
-  // grow-only capacities (bytes): a destroyed read set goes back to its thread's free list with its
-  // stream and buffers, and the next create reuses them (no hipMalloc / hipFree per batch)
+  gb::DevBuf<int64_t> d_trace;  // GB_FMI_FLAGS & 8 diagnostic (3 x nreads), allocated on demand
   int device = -1;
-  size_t cap_q2 = 0, cap_npos = 0;
-  size_t cap_qdb = 0, cap_q4 = 0, cap_lens = 0, cap_scratch = 0, cap_slots = 0, cap_ovf_pos = 0, cap_counts = 0,
-         cap_phase = 0, cap_offsets = 0, cap_temp = 0, cap_heavy = 0;
 };
 
 namespace {
@@ -1093,7 +1088,7 @@ namespace gbfmi {
 int ensure_occ32(gb_fmi_index *ix, hipStream_t s) {
   if (ix->d_occ32) return GB_OK;
   GB_ARG(ix->n < (1ll << 34), "FM index too large for 34-bit Occ32 counts (%lld rows)", (long long)ix->n);
-  GB_HIP(hipMalloc(&ix->d_occ32, sizeof(Occ32) * (size_t)ix->cp_size));
+  if (int st = ix->d_occ32.reserve((size_t)ix->cp_size)) return st;
   hipLaunchKernelGGL(compress_occ, dim3((unsigned)((ix->cp_size + 255) / 256)), dim3(256), 0, s, ix->d_occ,
                      ix->cp_size, ix->d_occ32);
   GB_HIP(hipGetLastError());
@@ -1120,12 +1115,7 @@ int check_fatal(gb_fmi_reads *R, const char *who) {
 // Compact the slots into d_out (exclusive scan already in d_offsets); tot = total SMEMs.
 int scatter_out(gb_fmi_reads *R, int64_t tot) {
   if (!R->scattered) {
-    if (tot > R->out_cap) {
-      (void)hipFree(R->d_out);
-      R->d_out = nullptr;
-      GB_HIP(hipMalloc(&R->d_out, sizeof(gb_smem) * (size_t)tot));
-      R->out_cap = tot;
-    }
+    if (int st = R->d_out.reserve((size_t)tot)) return st;
     if (tot) {
       hipLaunchKernelGGL(scatter_smems, dim3((R->nreads + 255) / 256), dim3(256), 0, R->stream, R->d_slots, R->d_big,
                          R->d_ovf_pos, R->d_counts, R->d_offsets, R->d_out, R->nreads);
@@ -1187,7 +1177,7 @@ int gb_fmi_debug_pack(int64_t n, const int64_t *ent, int64_t *ent_out, const int
 
 int gb_fmi_debug_trace(gb_fmi_reads *R, int64_t *out) {
   GB_ARG(R && out && R->ran, "gb_fmi_debug_trace: bad arguments");
-  GB_ARG(R->d_trace && R->cap_trace >= (size_t)R->nreads * 3 * sizeof(int64_t),
+  GB_ARG(R->d_trace && R->d_trace.capacity() >= (size_t)R->nreads * 3,
          "gb_fmi_debug_trace: the last search ran without GB_FMI_FLAGS & 8");
   GB_HIP(hipStreamSynchronize(R->stream));
   GB_HIP(hipMemcpy(out, R->d_trace, (size_t)R->nreads * 3 * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -1258,15 +1248,19 @@ int gb_fmi_index_load(const char *path, gb_fmi_index **out) {
   idx->sentinel = sentinel;
   idx->cp_size = cp_size;
   idx->sa_ns = ns;
-  hipError_t e = hipMalloc(&idx->d_occ, sizeof(gbfmi::CpOcc) * (size_t)cp_size);
-  if (e == hipSuccess)
-    e = gb::memcpy_big(idx->d_occ, occ.data(), sizeof(gbfmi::CpOcc) * (size_t)cp_size, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&idx->d_sa, sizeof(int64_t) * (size_t)ns);
-  if (e == hipSuccess) e = gb::memcpy_big(idx->d_sa, sa.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    gb::set_error("gb_fmi_index_load: %s", hipGetErrorString(e));
+  int st = idx->d_occ.reserve((size_t)cp_size);
+  if (!st) st = idx->d_sa.reserve((size_t)ns);
+  if (!st) {
+    hipError_t e = gb::memcpy_big(idx->d_occ, occ.data(), sizeof(gbfmi::CpOcc) * (size_t)cp_size, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = gb::memcpy_big(idx->d_sa, sa.data(), sizeof(int64_t) * (size_t)ns, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      gb::set_error("gb_fmi_index_load: %s", hipGetErrorString(e));
+      st = GB_ERR_HIP;
+    }
+  }
+  if (st) {
     gb_fmi_index_destroy(idx);
-    return GB_ERR_HIP;
+    return st;
   }
   *out = idx;
   return GB_OK;
@@ -1310,9 +1304,6 @@ int gb_fmi_index_sa(gb_fmi_index *idx, int64_t *dst, int64_t dst_entries) {
 
 int gb_fmi_index_destroy(gb_fmi_index *idx) {
   if (!idx) return GB_OK;
-  (void)hipFree(idx->d_occ);
-  (void)hipFree(idx->d_occ32);
-  (void)hipFree(idx->d_sa);
   delete idx;
   return GB_OK;
 }
@@ -1357,10 +1348,6 @@ int gb_fmi_reads_create(gb_fmi_index *idx, const uint8_t *enc_qdb, const int32_t
     e = hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking);
     for (auto &ev : R->ev)
       if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipMalloc(&R->d_ovf_list, gbfmi::kMaxOvf * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&R->d_big, (size_t)gbfmi::kMaxOvf * gbfmi::kBigCap * sizeof(gb_smem));
-    if (e == hipSuccess) e = hipMalloc(&R->d_ctl, 8 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&R->d_calls, 2 * sizeof(unsigned long long));
   }
   R->idx = idx;
   R->nreads = num_reads;
@@ -1370,34 +1357,36 @@ int gb_fmi_reads_create(gb_fmi_index *idx, const uint8_t *enc_qdb, const int32_t
   R->ran = R->scattered = false;
   R->total = 0;
   const size_t nr = (size_t)std::max(num_reads, 1);
-  auto reserve = [&](auto **p, size_t *cap, size_t bytes) {
-    if (e != hipSuccess || bytes <= *cap) return;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) *cap = bytes;
+  // every step runs only while none has failed: st is an allocation's failure, e a HIP call's
+  int st = GB_OK;
+  auto ok = [&] { return e == hipSuccess && !st; };
+  auto reserve = [&](auto &buf, size_t n) {  // a new block has at least 16 bytes
+    if (ok()) st = buf.reserve(n, std::max(n, 16 / sizeof(*buf.get())));
   };
-  reserve(&R->d_qdb, &R->cap_qdb, nr * (size_t)max_readlength);
-  reserve(&R->d_lens, &R->cap_lens, nr * sizeof(int32_t));
-  reserve(&R->d_scratch, &R->cap_scratch, (size_t)R->lanes * max_readlength * sizeof(gbfmi::PEnt));
-  reserve(&R->d_slots, &R->cap_slots, nr * gbfmi::kCap * sizeof(gb_smem));
-  reserve(&R->d_ovf_pos, &R->cap_ovf_pos, nr * sizeof(int32_t));
-  reserve(&R->d_counts, &R->cap_counts, nr * sizeof(int32_t));
-  reserve(&R->d_heavy, &R->cap_heavy, 2 * nr * sizeof(int32_t));
-  reserve(&R->d_phase, &R->cap_phase, nr * 3 * sizeof(int32_t));
-  reserve(&R->d_offsets, &R->cap_offsets, (nr + 1) * sizeof(int64_t));
-  if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, R->temp_bytes, R->d_counts, R->d_offsets, (int)nr);
-  reserve(&R->d_temp, &R->cap_temp, std::max<size_t>(R->temp_bytes, 16));
-  if (e == hipSuccess && num_reads) e = gb::memcpy_big(R->d_qdb, enc_qdb, (size_t)num_reads * max_readlength, hipMemcpyHostToDevice);
+  reserve(R->d_ovf_list, (size_t)gbfmi::kMaxOvf);
+  reserve(R->d_big, (size_t)gbfmi::kMaxOvf * gbfmi::kBigCap);
+  reserve(R->d_ctl, 8);
+  reserve(R->d_calls, 2);
+  reserve(R->d_qdb, nr * (size_t)max_readlength);
+  reserve(R->d_lens, nr);
+  reserve(R->d_scratch, (size_t)R->lanes * max_readlength);
+  reserve(R->d_slots, nr * gbfmi::kCap);
+  reserve(R->d_ovf_pos, nr);
+  reserve(R->d_counts, nr);
+  reserve(R->d_heavy, 2 * nr);
+  reserve(R->d_phase, nr * 3);
+  reserve(R->d_offsets, nr + 1);
+  if (ok())
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, R->temp_bytes, R->d_counts.get(), R->d_offsets.get(), (int)nr);
+  reserve(R->d_temp, std::max<size_t>(R->temp_bytes, 16));
+  if (ok() && num_reads) e = gb::memcpy_big(R->d_qdb, enc_qdb, (size_t)num_reads * max_readlength, hipMemcpyHostToDevice);
   R->q4_stride = (((max_readlength + 7) / 8) + 3) & ~3;  // 16-byte rows (smem_search staging)
-  reserve(&R->d_q4, &R->cap_q4, nr * (size_t)R->q4_stride * sizeof(uint32_t));
+  reserve(R->d_q4, nr * (size_t)R->q4_stride);
   R->q2_stride = (((max_readlength + 15) / 16) + 3) & ~3;
-  reserve(&R->d_q2, &R->cap_q2, nr * (size_t)R->q2_stride * sizeof(uint32_t));
-  reserve(&R->d_npos, &R->cap_npos, nr * sizeof(uint32_t));
-  if (e == hipSuccess && num_reads) e = hipMemcpy(R->d_lens, lens, (size_t)num_reads * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess && num_reads) {
+  reserve(R->d_q2, nr * (size_t)R->q2_stride);
+  reserve(R->d_npos, nr);
+  if (ok() && num_reads) e = hipMemcpy(R->d_lens, lens, (size_t)num_reads * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (ok() && num_reads) {
     const int64_t nt = (int64_t)num_reads * R->q4_stride;
     hipLaunchKernelGGL(gbfmi::pack_q4, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, R->stream, R->d_qdb,
                        max_readlength, num_reads, R->q4_stride, R->d_q4);
@@ -1412,11 +1401,11 @@ int gb_fmi_reads_create(gb_fmi_index *idx, const uint8_t *enc_qdb, const int32_t
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(R->stream);
   }
-  if (e != hipSuccess) {
-    gb::set_error("gb_fmi_reads_create: %s", hipGetErrorString(e));
+  if (!ok()) {
+    if (!st) gb::set_error("gb_fmi_reads_create: %s", hipGetErrorString(e));
     R->complete = false;  // a partly built read set is freed, never recycled
     gb_fmi_reads_destroy(R);
-    return GB_ERR_HIP;
+    return st ? st : GB_ERR_HIP;
   }
   R->complete = true;
   *out = R;
@@ -1432,11 +1421,6 @@ int gb_fmi_reads_destroy(gb_fmi_reads *R) {
     free_reads().push_back(R);
     return GB_OK;
   }
-  for (void *p : {(void *)R->d_qdb, (void *)R->d_q4, (void *)R->d_q2, (void *)R->d_npos, (void *)R->d_lens, (void *)R->d_scratch, (void *)R->d_slots,
-                  (void *)R->d_counts, (void *)R->d_phase, (void *)R->d_offsets, (void *)R->d_out,
-                  (void *)R->d_ctl, (void *)R->d_calls, R->d_temp, (void *)R->d_ovf_list,
-                  (void *)R->d_ovf_pos, (void *)R->d_big, (void *)R->d_trace, (void *)R->d_heavy})
-    (void)hipFree(p);
   for (auto ev : R->ev)
     if (ev) (void)hipEventDestroy(ev);
   if (R->stream) (void)hipStreamDestroy(R->stream);
@@ -1492,13 +1476,7 @@ int gb_fmi_search(gb_fmi_reads *R, int32_t min_seed_len) {
   A.trace = nullptr;
   if ((A.flags & 8) && R->nreads > 0) {
     const size_t bytes = (size_t)R->nreads * 3 * sizeof(int64_t);
-    if (bytes > R->cap_trace) {
-      (void)hipFree(R->d_trace);
-      R->d_trace = nullptr;
-      R->cap_trace = 0;
-      GB_HIP(hipMalloc(&R->d_trace, bytes));
-      R->cap_trace = bytes;
-    }
+    if (int st = R->d_trace.reserve((size_t)R->nreads * 3)) return st;
     GB_HIP(hipMemsetAsync(R->d_trace, 0, bytes, R->stream));
     A.trace = R->d_trace;
   }
@@ -1588,7 +1566,7 @@ int gb_fmi_search(gb_fmi_reads *R, int32_t min_seed_len) {
   }
   GB_HIP(hipEventRecord(R->ev[1], R->stream));
   if (R->nreads > 0) {
-    GB_HIP(hipcub::DeviceScan::ExclusiveSum(R->d_temp, R->temp_bytes, R->d_counts, R->d_offsets,
+    GB_HIP(hipcub::DeviceScan::ExclusiveSum(R->d_temp, R->temp_bytes, R->d_counts.get(), R->d_offsets.get(),
                                             R->nreads, R->stream));
   }
   GB_HIP(hipEventRecord(R->ev[2], R->stream));

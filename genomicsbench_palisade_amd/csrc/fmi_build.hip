@@ -248,28 +248,6 @@ inline unsigned grid(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) /
 // grid of the GRID_LOOP kernels: at most 2^20 blocks of 256 (2^28 work-items)
 inline unsigned grid_loop(int64_t n) { return std::min<unsigned>(grid(n), 1u << 20); }
 
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { (void)hipFree(p); }
-  template <typename T>
-  T *as() { return static_cast<T *>(p); }
-};
-
-#define GB_HIPX(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) {                                                                   \
-      gb::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return GB_ERR_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
-
-template <typename T>
-int dalloc(DevBuf &b, int64_t n) {
-  GB_HIPX(hipMalloc(&b.p, sizeof(T) * (size_t)std::max<int64_t>(n, 1)));
-  return GB_OK;
-}
-
 // rows of one sort (the first sort's buckets, the doubling chunks): GB_FMI_BUILD_CHUNK, default and
 // maximum 2^30 (the doubling key's relative-rank field); tests lower it to exercise the chunking
 int64_t chunk_cap() {
@@ -290,27 +268,29 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
   const int64_t N = 2 * G;
   const int64_t C = std::min<int64_t>(chunk_cap(), N);
   hipStream_t s = 0;
-  DevBuf d_ref, d_text, d_sa, d_rank, d_U, d_U2, d_hist, d_cnt, d_key, d_key_alt, d_val, d_val_alt, d_head, d_iota,
-      d_tied, d_tmp;
+  gb::DevBuf<uint8_t> d_ref, d_text, d_tied, d_tmp;
+  gb::DevBuf<I> d_sa, d_rank, d_U, d_U2, d_val, d_val_alt, d_head, d_iota;
+  gb::DevBuf<unsigned long long> d_hist, d_cnt;
+  gb::DevBuf<uint64_t> d_key, d_key_alt;
   constexpr int64_t kBins = 1ll << kPrefixBits;
   int st;
-  if ((st = dalloc<uint8_t>(d_ref, G)) || (st = dalloc<uint8_t>(d_text, N)) || (st = dalloc<I>(d_sa, N)) ||
-      (st = dalloc<I>(d_rank, N)) || (st = dalloc<I>(d_U, N)) || (st = dalloc<unsigned long long>(d_hist, kBins)) ||
-      (st = dalloc<unsigned long long>(d_cnt, 2)) || (st = dalloc<uint64_t>(d_key, C)) ||
-      (st = dalloc<uint64_t>(d_key_alt, C)) || (st = dalloc<I>(d_val, C)) || (st = dalloc<I>(d_val_alt, C)) ||
-      (st = dalloc<I>(d_head, C)) || (st = dalloc<I>(d_iota, C)) || (st = dalloc<uint8_t>(d_tied, C)))
+  if ((st = d_ref.reserve((size_t)G)) || (st = d_text.reserve((size_t)N)) || (st = d_sa.reserve((size_t)N)) ||
+      (st = d_rank.reserve((size_t)N)) || (st = d_U.reserve((size_t)N)) || (st = d_hist.reserve((size_t)kBins)) ||
+      (st = d_cnt.reserve(2)) || (st = d_key.reserve((size_t)C)) || (st = d_key_alt.reserve((size_t)C)) ||
+      (st = d_val.reserve((size_t)C)) || (st = d_val_alt.reserve((size_t)C)) || (st = d_head.reserve((size_t)C)) ||
+      (st = d_iota.reserve((size_t)C)) || (st = d_tied.reserve((size_t)C)))
     return st;
-  I *const sa = d_sa.as<I>();
-  I *const rank = d_rank.as<I>();
-  unsigned long long *const cnt = d_cnt.as<unsigned long long>();
-  GB_HIPX(gb::memcpy_big(d_ref.p, ref_codes, (size_t)G, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(make_text, dim3(grid_loop(G)), dim3(256), 0, s, d_ref.as<uint8_t>(), G, d_text.as<uint8_t>());
-  GB_HIPX(hipMemsetAsync(d_hist.p, 0, sizeof(unsigned long long) * kBins, s));
-  hipLaunchKernelGGL(prefix_hist, dim3(grid_loop(N)), dim3(256), 0, s, d_text.as<uint8_t>(), N,
-                     d_hist.as<unsigned long long>());
-  GB_HIPX(hipGetLastError());
+  I *const sa = d_sa.get();
+  I *const rank = d_rank.get();
+  unsigned long long *const cnt = d_cnt.get();
+  GB_HIP(gb::memcpy_big(d_ref.get(), ref_codes, (size_t)G, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(make_text, dim3(grid_loop(G)), dim3(256), 0, s, d_ref.get(), G, d_text.get());
+  GB_HIP(hipMemsetAsync(d_hist.get(), 0, sizeof(unsigned long long) * kBins, s));
+  hipLaunchKernelGGL(prefix_hist, dim3(grid_loop(N)), dim3(256), 0, s, d_text.get(), N,
+                     d_hist.get());
+  GB_HIP(hipGetLastError());
   std::vector<unsigned long long> hist((size_t)kBins);
-  GB_HIPX(hipMemcpy(hist.data(), d_hist.p, sizeof(unsigned long long) * kBins, hipMemcpyDeviceToHost));
+  GB_HIP(hipMemcpy(hist.data(), d_hist.get(), sizeof(unsigned long long) * kBins, hipMemcpyDeviceToHost));
 
   // buckets: runs of consecutive prefixes of at most C suffixes, in suffix order
   std::vector<Bucket> buckets;
@@ -337,17 +317,17 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
   // temp storage sized for the largest operation over C elements
   size_t tb_sort = 0, tb_scan = 0, tb_sum = 0, tb_sel = 0;
   {
-    hipcub::DoubleBuffer<uint64_t> kb(d_key.as<uint64_t>(), d_key_alt.as<uint64_t>());
-    hipcub::DoubleBuffer<I> vb(d_val.as<I>(), d_val_alt.as<I>());
-    GB_HIPX(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, kb, vb, (int)C, 0, 64, s));
-    GB_HIPX(hipcub::DeviceScan::InclusiveScan(nullptr, tb_scan, d_head.as<I>(), d_head.as<I>(), hipcub::Max(),
+    hipcub::DoubleBuffer<uint64_t> kb(d_key.get(), d_key_alt.get());
+    hipcub::DoubleBuffer<I> vb(d_val.get(), d_val_alt.get());
+    GB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, kb, vb, (int)C, 0, 64, s));
+    GB_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb_scan, d_head.get(), d_head.get(), hipcub::Max(),
                                               (int)C, s));
-    GB_HIPX(hipcub::DeviceScan::InclusiveSum(nullptr, tb_sum, d_head.as<I>(), d_head.as<I>(), (int)C, s));
-    GB_HIPX(hipcub::DeviceSelect::Flagged(nullptr, tb_sel, d_iota.as<I>(), d_tied.as<uint8_t>(), d_U.as<I>(),
+    GB_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb_sum, d_head.get(), d_head.get(), (int)C, s));
+    GB_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb_sel, d_iota.get(), d_tied.get(), d_U.get(),
                                           cnt + 1, (int)C, s));
   }
   const size_t tb = std::max({tb_sort, tb_scan, tb_sum, tb_sel, (size_t)16});
-  if ((st = dalloc<uint8_t>(d_tmp, (int64_t)tb))) return st;
+  if ((st = d_tmp.reserve(tb))) return st;
   size_t tbv = tb;
 
   // (1) each bucket sorted by the suffixes' first 21 bases into its rows of the SA; ranks = group
@@ -355,51 +335,51 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
   int64_t nu = 0;
   for (const Bucket &b : buckets) {
     const int64_t m = b.size;
-    GB_HIPX(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(bucket_keys<I>, dim3(grid_loop(N)), dim3(256), 0, s, d_text.as<uint8_t>(), N, b.p0, b.p1,
-                       d_key.as<uint64_t>(), d_val.as<I>(), cnt);
-    hipcub::DoubleBuffer<uint64_t> kb(d_key.as<uint64_t>(), d_key_alt.as<uint64_t>());
-    hipcub::DoubleBuffer<I> vb(d_val.as<I>(), d_val_alt.as<I>());
+    GB_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(bucket_keys<I>, dim3(grid_loop(N)), dim3(256), 0, s, d_text.get(), N, b.p0, b.p1,
+                       d_key.get(), d_val.get(), cnt);
+    hipcub::DoubleBuffer<uint64_t> kb(d_key.get(), d_key_alt.get());
+    hipcub::DoubleBuffer<I> vb(d_val.get(), d_val_alt.get());
     tbv = tb;
-    GB_HIPX(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tbv, kb, vb, (int)m, 0, 63, s));
+    GB_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tbv, kb, vb, (int)m, 0, 63, s));
     const uint64_t *ks = kb.Current();
     const I *vs = vb.Current();
     hipLaunchKernelGGL(copy_vals<I>, dim3(grid(m)), dim3(256), 0, s, vs, m, sa + b.off);
     hipLaunchKernelGGL(group_heads<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, (const I *)nullptr, b.off,
-                       d_head.as<I>());
+                       d_head.get());
     tbv = tb;
-    GB_HIPX(hipcub::DeviceScan::InclusiveScan(d_tmp.p, tbv, d_head.as<I>(), d_head.as<I>(), hipcub::Max(), (int)m, s));
-    hipLaunchKernelGGL(scatter_rank<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, vs, (const I *)d_head.as<I>(), rank,
-                       d_tied.as<uint8_t>());
-    hipLaunchKernelGGL(iota_from<I>, dim3(grid(m)), dim3(256), 0, s, d_iota.as<I>(), m, b.off);
+    GB_HIP(hipcub::DeviceScan::InclusiveScan(d_tmp.get(), tbv, d_head.get(), d_head.get(), hipcub::Max(), (int)m, s));
+    hipLaunchKernelGGL(scatter_rank<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, vs, (const I *)d_head.get(), rank,
+                       d_tied.get());
+    hipLaunchKernelGGL(iota_from<I>, dim3(grid(m)), dim3(256), 0, s, d_iota.get(), m, b.off);
     tbv = tb;
-    GB_HIPX(hipcub::DeviceSelect::Flagged(d_tmp.p, tbv, d_iota.as<I>(), d_tied.as<uint8_t>(), d_U.as<I>() + nu,
+    GB_HIP(hipcub::DeviceSelect::Flagged(d_tmp.get(), tbv, d_iota.get(), d_tied.get(), d_U.get() + nu,
                                           cnt + 1, (int)m, s));
-    GB_HIPX(hipGetLastError());
+    GB_HIP(hipGetLastError());
     unsigned long long got[2] = {0, 0};
-    GB_HIPX(hipMemcpy(got, cnt, sizeof(got), hipMemcpyDeviceToHost));
+    GB_HIP(hipMemcpy(got, cnt, sizeof(got), hipMemcpyDeviceToHost));
     if ((int64_t)got[0] != m) {
       gb::set_error("gb_fmi_index_build: bucket holds %llu suffixes, histogram said %lld", got[0], (long long)m);
       return GB_ERR_HIP;
     }
     nu += (int64_t)got[1];
   }
-  if (nu > 0 && (st = dalloc<I>(d_U2, nu))) return st;
+  if (nu > 0 && (st = d_U2.reserve((size_t)nu))) return st;
 
   // (2) prefix doubling on the tied rows only, in chunks of whole groups (a chunk's ranks are
   //     refined before the next chunk reads them, which only sharpens its keys: Larsson-Sadakane)
   for (int64_t h = kKmer; nu > 0; h *= 2) {
     GB_ARG(h < 2 * N, "gb_fmi_index_build: doubling did not converge");
-    I *U = d_U.as<I>(), *U2 = d_U2.as<I>();
+    I *U = d_U.get(), *U2 = d_U2.get();
     int64_t nu2 = 0;
     for (int64_t t0 = 0; t0 < nu;) {
       int64_t t1 = std::min(t0 + C, nu);
       if (t1 < nu) {  // end the chunk at the last group start in (t0, t1]
-        GB_HIPX(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
+        GB_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
         hipLaunchKernelGGL(last_group_start<I>, dim3(grid(t1 - t0)), dim3(256), 0, s, U, t0, t1, (const I *)sa,
                            (const I *)rank, cnt);
         unsigned long long cut = 0;
-        GB_HIPX(hipMemcpy(&cut, cnt, sizeof(cut), hipMemcpyDeviceToHost));
+        GB_HIP(hipMemcpy(&cut, cnt, sizeof(cut), hipMemcpyDeviceToHost));
         if (cut == 0) {
           gb::set_error("gb_fmi_index_build: a tied group exceeds the chunk limit %lld", (long long)C);
           return GB_ERR_ARG;
@@ -408,34 +388,34 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
       }
       const int64_t m = t1 - t0;
       hipLaunchKernelGGL(group_start_flags<I>, dim3(grid(m)), dim3(256), 0, s, (const I *)(U + t0), m, (const I *)sa,
-                         (const I *)rank, d_head.as<I>());
+                         (const I *)rank, d_head.get());
       tbv = tb;
-      GB_HIPX(hipcub::DeviceScan::InclusiveSum(d_tmp.p, tbv, d_head.as<I>(), d_head.as<I>(), (int)m, s));
+      GB_HIP(hipcub::DeviceScan::InclusiveSum(d_tmp.get(), tbv, d_head.get(), d_head.get(), (int)m, s));
       hipLaunchKernelGGL(doubling_keys<I>, dim3(grid(m)), dim3(256), 0, s, U + t0, m, (const I *)sa, (const I *)rank,
-                         N, h, (const I *)d_head.as<I>(), d_key.as<uint64_t>(), d_val.as<I>());
-      hipcub::DoubleBuffer<uint64_t> kb(d_key.as<uint64_t>(), d_key_alt.as<uint64_t>());
-      hipcub::DoubleBuffer<I> vb(d_val.as<I>(), d_val_alt.as<I>());
+                         N, h, (const I *)d_head.get(), d_key.get(), d_val.get());
+      hipcub::DoubleBuffer<uint64_t> kb(d_key.get(), d_key_alt.get());
+      hipcub::DoubleBuffer<I> vb(d_val.get(), d_val_alt.get());
       tbv = tb;
-      GB_HIPX(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tbv, kb, vb, (int)m, 0, 64, s));
+      GB_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tbv, kb, vb, (int)m, 0, 64, s));
       const uint64_t *ks = kb.Current();
       const I *vs = vb.Current();
       hipLaunchKernelGGL(write_back<I>, dim3(grid(m)), dim3(256), 0, s, (const I *)(U + t0), m, vs, sa);
       hipLaunchKernelGGL(group_heads<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, (const I *)(U + t0), (int64_t)0,
-                         d_head.as<I>());
+                         d_head.get());
       tbv = tb;
-      GB_HIPX(hipcub::DeviceScan::InclusiveScan(d_tmp.p, tbv, d_head.as<I>(), d_head.as<I>(), hipcub::Max(), (int)m,
+      GB_HIP(hipcub::DeviceScan::InclusiveScan(d_tmp.get(), tbv, d_head.get(), d_head.get(), hipcub::Max(), (int)m,
                                                 s));
-      hipLaunchKernelGGL(scatter_rank<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, vs, (const I *)d_head.as<I>(), rank,
-                         d_tied.as<uint8_t>());
+      hipLaunchKernelGGL(scatter_rank<I>, dim3(grid(m)), dim3(256), 0, s, ks, m, vs, (const I *)d_head.get(), rank,
+                         d_tied.get());
       tbv = tb;
-      GB_HIPX(hipcub::DeviceSelect::Flagged(d_tmp.p, tbv, U + t0, d_tied.as<uint8_t>(), U2 + nu2, cnt + 1, (int)m, s));
-      GB_HIPX(hipGetLastError());
+      GB_HIP(hipcub::DeviceSelect::Flagged(d_tmp.get(), tbv, U + t0, d_tied.get(), U2 + nu2, cnt + 1, (int)m, s));
+      GB_HIP(hipGetLastError());
       unsigned long long got = 0;
-      GB_HIPX(hipMemcpy(&got, cnt + 1, sizeof(got), hipMemcpyDeviceToHost));
+      GB_HIP(hipMemcpy(&got, cnt + 1, sizeof(got), hipMemcpyDeviceToHost));
       nu2 += (int64_t)got;
       t0 = t1;
     }
-    std::swap(d_U.p, d_U2.p);
+    std::swap(d_U, d_U2);
     nu = nu2;
   }
 
@@ -450,42 +430,33 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
     }
   } guard{new gb_fmi_index()};
   gb_fmi_index *const idx = guard.p;
-  GB_HIPX(hipGetDevice(&idx->device));
-  hipError_t e = hipMalloc(&idx->d_occ, sizeof(CpOcc) * (size_t)nblocks);
-  if (e != hipSuccess) {
-    gb::set_error("gb_fmi_index_build: %s", hipGetErrorString(e));
-    return GB_ERR_HIP;
-  }
+  GB_HIP(hipGetDevice(&idx->device));
+  if ((st = idx->d_occ.reserve((size_t)nblocks))) return st;
   // the sort buffers are dead now: free them before the per-block count arrays
-  for (DevBuf *b : {&d_U, &d_U2, &d_key, &d_key_alt, &d_val, &d_val_alt, &d_head, &d_iota, &d_rank}) {
-    (void)hipFree(b->p);
-    b->p = nullptr;
-  }
-  DevBuf d_cnt4, d_scan;
-  if ((st = dalloc<int64_t>(d_cnt4, 4 * nblocks)) || (st = dalloc<int64_t>(d_scan, 4 * nblocks))) {
-    return st;
-  }
-  hipLaunchKernelGGL(occ_blocks<I>, dim3(grid(nblocks)), dim3(256), 0, s, d_text.as<uint8_t>(), (const I *)sa, N,
-                     nblocks, idx->d_occ, d_cnt4.as<int64_t>());
+  for (auto *b : {&d_U, &d_U2, &d_val, &d_val_alt, &d_head, &d_iota, &d_rank}) b->reset();
+  d_key.reset();
+  d_key_alt.reset();
+  gb::DevBuf<int64_t> d_cnt4, d_scan;
+  if ((st = d_cnt4.reserve(4 * (size_t)nblocks)) || (st = d_scan.reserve(4 * (size_t)nblocks))) return st;
+  hipLaunchKernelGGL(occ_blocks<I>, dim3(grid(nblocks)), dim3(256), 0, s, d_text.get(), (const I *)sa, N,
+                     nblocks, idx->d_occ, d_cnt4.get());
   size_t tb64 = 0;
-  GB_HIPX(hipcub::DeviceScan::ExclusiveSum(nullptr, tb64, d_cnt4.as<int64_t>(), d_scan.as<int64_t>(), (int)nblocks, s));
-  DevBuf d_tmp64;
-  if ((st = dalloc<uint8_t>(d_tmp64, (int64_t)tb64 + 16))) {
-    return st;
-  }
+  GB_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb64, d_cnt4.get(), d_scan.get(), (int)nblocks, s));
+  gb::DevBuf<uint8_t> d_tmp64;
+  if ((st = d_tmp64.reserve(tb64 + 16))) return st;
   for (int q = 0; q < 4; q++) {
     size_t t2 = tb64;
-    GB_HIPX(hipcub::DeviceScan::ExclusiveSum(d_tmp64.p, t2, d_cnt4.as<int64_t>() + q * nblocks,
-                                             d_scan.as<int64_t>() + q * nblocks, (int)nblocks, s));
+    GB_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp64.get(), t2, d_cnt4.get() + q * nblocks,
+                                             d_scan.get() + q * nblocks, (int)nblocks, s));
   }
-  hipLaunchKernelGGL(occ_counts, dim3(grid(nblocks)), dim3(256), 0, s, idx->d_occ, d_scan.as<int64_t>(), nblocks, n);
-  int64_t *const d_sent = d_scan.as<int64_t>();  // the scans are consumed by occ_counts above (same stream)
-  GB_HIPX(hipMemsetAsync(d_sent, 0xff, sizeof(int64_t), s));
+  hipLaunchKernelGGL(occ_counts, dim3(grid(nblocks)), dim3(256), 0, s, idx->d_occ, d_scan.get(), nblocks, n);
+  int64_t *const d_sent = d_scan.get();  // the scans are consumed by occ_counts above (same stream)
+  GB_HIP(hipMemsetAsync(d_sent, 0xff, sizeof(int64_t), s));
   hipLaunchKernelGGL(find_sentinel<I>, dim3(grid_loop(N)), dim3(256), 0, s, (const I *)sa, N, d_sent);
-  GB_HIPX(hipGetLastError());
-  GB_HIPX(hipDeviceSynchronize());
+  GB_HIP(hipGetLastError());
+  GB_HIP(hipDeviceSynchronize());
   int64_t sentinel = -1;
-  GB_HIPX(hipMemcpy(&sentinel, d_sent, sizeof(int64_t), hipMemcpyDeviceToHost));
+  GB_HIP(hipMemcpy(&sentinel, d_sent, sizeof(int64_t), hipMemcpyDeviceToHost));
   // base totals from the text (the BWT is a permutation of it plus '$')
   int64_t c4[4] = {0, 0, 0, 0};
   for (int64_t i = 0; i < G; i++) {
@@ -507,28 +478,24 @@ int build_impl(const uint8_t *ref_codes, int64_t G, const char *out_path, gb_fmi
   //     (build_fm_index, FMI_search.cpp:206-347)
   const int64_t ns = (n >> 3) + 1;
   idx->sa_ns = ns;
-  if (hipMalloc(&idx->d_sa, sizeof(int64_t) * (size_t)ns) != hipSuccess) {
-    gb::set_error("gb_fmi_index_build: out of device memory (sampled SA)");
-    return GB_ERR_HIP;
-  }
+  if ((st = idx->d_sa.reserve((size_t)ns))) return st;
   if (!out_path) {
     hipLaunchKernelGGL(sample_sa<I>, dim3(grid(ns)), dim3(256), 0, s, (const I *)sa, N, ns, (int8_t *)nullptr,
                        (uint32_t *)nullptr, idx->d_sa);
-    GB_HIPX(hipGetLastError());
-    GB_HIPX(hipDeviceSynchronize());
+    GB_HIP(hipGetLastError());
+    GB_HIP(hipDeviceSynchronize());
   } else {
-    DevBuf d_ms, d_ls;
-    if ((st = dalloc<int8_t>(d_ms, ns)) || (st = dalloc<uint32_t>(d_ls, ns))) {
-      return st;
-    }
-    hipLaunchKernelGGL(sample_sa<I>, dim3(grid(ns)), dim3(256), 0, s, (const I *)sa, N, ns, d_ms.as<int8_t>(),
-                       d_ls.as<uint32_t>(), idx->d_sa);
+    gb::DevBuf<int8_t> d_ms;
+    gb::DevBuf<uint32_t> d_ls;
+    if ((st = d_ms.reserve((size_t)ns)) || (st = d_ls.reserve((size_t)ns))) return st;
+    hipLaunchKernelGGL(sample_sa<I>, dim3(grid(ns)), dim3(256), 0, s, (const I *)sa, N, ns, d_ms.get(),
+                       d_ls.get(), idx->d_sa);
     std::vector<CpOcc> occ((size_t)nblocks);
     std::vector<int8_t> ms((size_t)ns);
     std::vector<uint32_t> ls((size_t)ns);
-    GB_HIPX(gb::memcpy_big(occ.data(), idx->d_occ, sizeof(CpOcc) * (size_t)nblocks, hipMemcpyDeviceToHost));
-    GB_HIPX(gb::memcpy_big(ms.data(), d_ms.p, (size_t)ns, hipMemcpyDeviceToHost));
-    GB_HIPX(gb::memcpy_big(ls.data(), d_ls.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
+    GB_HIP(gb::memcpy_big(occ.data(), idx->d_occ, sizeof(CpOcc) * (size_t)nblocks, hipMemcpyDeviceToHost));
+    GB_HIP(gb::memcpy_big(ms.data(), d_ms.get(), (size_t)ns, hipMemcpyDeviceToHost));
+    GB_HIP(gb::memcpy_big(ls.data(), d_ls.get(), 4 * (size_t)ns, hipMemcpyDeviceToHost));
     FILE *fp = fopen(out_path, "wb");
     if (!fp) {
       gb::set_error("gb_fmi_index_build: cannot write %s", out_path);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gb_common.h"
+
 namespace gbfmi {
 
 // CP_OCC (tools/bwa-mem2/src/FMI_search.h:59-63): occurrence counts before row 64*i and one-hot
@@ -141,10 +143,10 @@ struct gb_fmi_index {
   int64_t count[5] = {0};   // after the load-time +1 (FMI_search.cpp:763-768)
   int64_t sentinel = -1;
   int64_t cp_size = 0;      // (n >> 6) + 1 entries
-  gbfmi::CpOcc *d_occ = nullptr;
-  gbfmi::Occ32 *d_occ32 = nullptr;  // cp_size blocks, built from d_occ on first use
-  int64_t sa_ns = 0;        // (n >> 3) + 1 sampled SA entries (SA_COMPX = 3, macro.h:64-66)
-  int64_t *d_sa = nullptr;  // sa_ms_byte << 32 + sa_ls_word, one int64 per sampled row
+  gb::DevBuf<gbfmi::CpOcc> d_occ;
+  gb::DevBuf<gbfmi::Occ32> d_occ32;  // cp_size blocks, built from d_occ on first use
+  int64_t sa_ns = 0;          // (n >> 3) + 1 sampled SA entries (SA_COMPX = 3, macro.h:64-66)
+  gb::DevBuf<int64_t> d_sa;   // sa_ms_byte << 32 + sa_ls_word, one int64 per sampled row
 };
 
 struct gb_fmi_reads;

@@ -42,16 +42,12 @@ struct SaJob {
   int64_t nsmem = 0, ncoords = 0;
   int32_t max_occ = 0;
   const gb_smem *d_smems = nullptr;  // borrowed (read set) or d_smems_own
-  gb_smem *d_smems_own = nullptr;
-  int64_t smem_own_cap = 0;
-  int64_t *d_cnt = nullptr;   // per SMEM
-  int64_t *d_coff = nullptr;  // nsmem + 1 (coff[0] = 0)
-  int64_t cnt_cap = 0;
-  int64_t *d_rows = nullptr, *d_coords = nullptr;
-  int64_t coord_cap = 0;
-  unsigned long long *d_ctl = nullptr;  // [0] next row, [1] LF steps
-  void *d_temp = nullptr;
-  size_t temp_cap = 0;
+  gb::DevBuf<gb_smem> d_smems_own;
+  gb::DevBuf<int64_t> d_cnt;   // per SMEM
+  gb::DevBuf<int64_t> d_coff;  // nsmem + 1 (coff[0] = 0)
+  gb::DevBuf<int64_t> d_rows, d_coords;
+  gb::DevBuf<unsigned long long> d_ctl;  // [0] next row, [1] LF steps
+  gb::DevBuf<uint8_t> d_temp;
   bool ran = false;
 };
 
@@ -172,9 +168,6 @@ inline unsigned grid1(int64_t n, int bs = 256) { return (unsigned)((n + bs - 1) 
 void sa_job_destroy(SaJob *J) {
   if (!J) return;
   if (J->stream) (void)hipStreamSynchronize(J->stream);
-  for (void *p : {(void *)J->d_smems_own, (void *)J->d_cnt, (void *)J->d_coff, (void *)J->d_rows,
-                  (void *)J->d_coords, (void *)J->d_ctl, J->d_temp})
-    (void)hipFree(p);
   for (auto e : J->ev)
     if (e) (void)hipEventDestroy(e);
   if (J->own_stream && J->stream) (void)hipStreamDestroy(J->stream);
@@ -195,37 +188,22 @@ int job_create(hipStream_t borrowed, SaJob **out) {
   }
   for (auto &ev : J->ev)
     if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e == hipSuccess) e = hipMalloc(&J->d_ctl, 2 * sizeof(unsigned long long));
-  if (e != hipSuccess) {
+  int st = GB_ERR_HIP;
+  if (e == hipSuccess)
+    st = J->d_ctl.reserve(2);
+  else
     gb::set_error("SA lookup: %s", hipGetErrorString(e));
+  if (st) {
     sa_job_destroy(J);
-    return GB_ERR_HIP;
+    return st;
   }
   *out = J;
   return GB_OK;
 }
 
-template <typename T>
-int grow(T *&p, int64_t &cap, int64_t need) {
-  if (need <= cap) return GB_OK;
-  (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  GB_HIP(hipMalloc(&p, sizeof(T) * (size_t)std::max<int64_t>(need, 1)));
-  cap = need;
-  return GB_OK;
-}
-
 int grow_coords(SaJob *J, int64_t need) {
-  if (need <= J->coord_cap) return GB_OK;
-  (void)hipFree(J->d_rows);
-  (void)hipFree(J->d_coords);
-  J->d_rows = J->d_coords = nullptr;
-  J->coord_cap = 0;
-  GB_HIP(hipMalloc(&J->d_rows, sizeof(int64_t) * (size_t)std::max<int64_t>(need, 1)));
-  GB_HIP(hipMalloc(&J->d_coords, sizeof(int64_t) * (size_t)std::max<int64_t>(need, 1)));
-  J->coord_cap = need;
-  return GB_OK;
+  if (int st = J->d_rows.reserve((size_t)need)) return st;
+  return J->d_coords.reserve((size_t)need);
 }
 
 // per-SMEM coordinate counts and their offsets; sizes the row/coord buffers (one host sync)
@@ -233,28 +211,17 @@ int prepare(SaJob *J, const gb_smem *d_smems, int64_t nsmem, int32_t max_occ) {
   J->d_smems = d_smems;
   J->nsmem = nsmem;
   J->max_occ = max_occ;
-  int64_t cap = J->cnt_cap;
-  if (nsmem + 1 > cap) {
-    int st = grow(J->d_cnt, J->cnt_cap, nsmem + 1);
-    if (st) return st;
-    (void)hipFree(J->d_coff);
-    J->d_coff = nullptr;
-    GB_HIP(hipMalloc(&J->d_coff, sizeof(int64_t) * (size_t)(nsmem + 1)));
-  }
+  if (int st = J->d_cnt.reserve((size_t)nsmem + 1)) return st;
+  if (int st = J->d_coff.reserve((size_t)nsmem + 1)) return st;
   GB_HIP(hipMemsetAsync(J->d_coff, 0, sizeof(int64_t), J->stream));
   J->ncoords = 0;
   if (nsmem > 0) {
     hipLaunchKernelGGL(sa_counts, dim3(grid1(nsmem)), dim3(256), 0, J->stream, d_smems, nsmem, max_occ, J->d_cnt);
     GB_HIP(hipGetLastError());
     size_t tb = 0;
-    GB_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, J->d_cnt, J->d_coff + 1, (int)nsmem, J->stream));
-    if (tb > J->temp_cap) {
-      (void)hipFree(J->d_temp);
-      J->d_temp = nullptr;
-      GB_HIP(hipMalloc(&J->d_temp, tb));
-      J->temp_cap = tb;
-    }
-    GB_HIP(hipcub::DeviceScan::InclusiveSum(J->d_temp, tb, J->d_cnt, J->d_coff + 1, (int)nsmem, J->stream));
+    GB_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, J->d_cnt.get(), J->d_coff + 1, (int)nsmem, J->stream));
+    if (int st = J->d_temp.reserve(tb)) return st;
+    GB_HIP(hipcub::DeviceScan::InclusiveSum(J->d_temp, tb, J->d_cnt.get(), J->d_coff + 1, (int)nsmem, J->stream));
     GB_HIP(hipMemcpyAsync(&J->ncoords, J->d_coff + nsmem, sizeof(int64_t), hipMemcpyDeviceToHost, J->stream));
     GB_HIP(hipStreamSynchronize(J->stream));
   }
@@ -356,7 +323,7 @@ int gb_fmi_sa_entries(gb_fmi_index *idx, const gb_smem *smems, int64_t n, int32_
   SaJob *J = nullptr;
   int st = job_create(nullptr, &J);
   if (!st) st = check_index(idx, J->stream);
-  if (!st) st = grow(J->d_smems_own, J->smem_own_cap, n);
+  if (!st) st = J->d_smems_own.reserve((size_t)n);
   if (!st && n && gb::memcpy_big(J->d_smems_own, smems, sizeof(gb_smem) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
     gb::set_error("gb_fmi_sa_entries: upload failed");
     st = GB_ERR_HIP;

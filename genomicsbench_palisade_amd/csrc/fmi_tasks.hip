@@ -383,42 +383,19 @@ __global__ __launch_bounds__(64) void fmi_task_wave(TaskArgs A) {
 
 // Per host thread and device: stream, grow-only device buffers and a pinned staging buffer (the
 // reference's methods are called from OpenMP threads sharing one FMI_search object).
-struct Workspace {
+struct Workspace {  // never deleted (workspace())
   int device = -1;
   hipStream_t stream = nullptr;
-  void *buf[10] = {nullptr};
-  size_t cap[10] = {0};
-  uint8_t *h = nullptr;  // pinned: uploads are packed here, downloads land here
-  size_t hcap = 0;
-  ~Workspace() {
-    if (device < 0) return;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(device);
-    for (void *p : buf) (void)hipFree(p);
-    if (h) (void)hipHostFree(h);
-    if (stream) (void)hipStreamDestroy(stream);
-    (void)hipSetDevice(cur);
-  }
-  hipError_t ensure(int slot, size_t bytes) {
+  gb::DevBuf<uint8_t> buf[10];
+  gb::PinnedBuf<uint8_t> h;  // uploads are packed here, downloads land here
+  // growth policy: a new block is half again as large as the need (at least 64 B / 1 MiB)
+  int ensure(int slot, size_t bytes) {
     bytes = std::max<size_t>(bytes, 64);
-    if (cap[slot] >= bytes) return hipSuccess;
-    (void)hipFree(buf[slot]);
-    buf[slot] = nullptr;
-    cap[slot] = 0;
-    hipError_t e = hipMalloc(&buf[slot], bytes + bytes / 2);
-    if (e == hipSuccess) cap[slot] = bytes + bytes / 2;
-    return e;
+    return buf[slot].reserve(bytes, bytes + bytes / 2);
   }
-  hipError_t ensure_host(size_t bytes) {
+  int ensure_host(size_t bytes) {
     bytes = std::max<size_t>(bytes, 1 << 20);
-    if (hcap >= bytes) return hipSuccess;
-    if (h) (void)hipHostFree(h);
-    h = nullptr;
-    hcap = 0;
-    hipError_t e = hipHostMalloc((void **)&h, bytes + bytes / 2, hipHostMallocDefault);
-    if (e == hipSuccess) hcap = bytes + bytes / 2;
-    return e;
+    return h.reserve(bytes, bytes + bytes / 2);
   }
 };
 
@@ -498,15 +475,15 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
   {
     const size_t o_lens = up256((size_t)extent), o_offs = o_lens + up256(4 * (size_t)nrid),
                  bytes = o_offs + 4 * (size_t)nrid;
-    GB_HIP(W.ensure(0, bytes));
-    GB_HIP(W.ensure_host(bytes));
+    if (int st = W.ensure(0, bytes)) return st;
+    if (int st = W.ensure_host(bytes)) return st;
     std::memcpy(W.h, qdb, (size_t)extent);
     std::memcpy(W.h + o_lens, lens, 4 * (size_t)nrid);
     std::memcpy(W.h + o_offs, offs, 4 * (size_t)nrid);
     GB_HIP(hipMemcpyAsync(W.buf[0], W.h, bytes, hipMemcpyHostToDevice, s));
-    A.qdb = (const uint8_t *)W.buf[0];
-    A.lens = (const int32_t *)((uint8_t *)W.buf[0] + o_lens);
-    A.offs = (const int32_t *)((uint8_t *)W.buf[0] + o_offs);
+    A.qdb = (const uint8_t *)W.buf[0].get();
+    A.lens = (const int32_t *)((uint8_t *)W.buf[0].get() + o_lens);
+    A.offs = (const int32_t *)((uint8_t *)W.buf[0].get() + o_offs);
     GB_HIP(hipStreamSynchronize(s));  // W.h is reused below
   }
 
@@ -534,13 +511,13 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
                  c_toff = c_tcalls + up256(4 * (size_t)n), c_np = c_toff + up256(4 * (size_t)n),
                  ctl_bytes = c_np + 2 * (size_t)n;
     const size_t rec_bytes = sizeof(TSmem) * (size_t)n * cap;
-    hipError_t e = W.ensure(3, in_bytes);
-    if (e == hipSuccess) e = W.ensure(6, rec_bytes);
-    if (e == hipSuccess) e = W.ensure(7, ctl_bytes);
-    if (e == hipSuccess) e = W.ensure(8, sizeof(TEnt) * (size_t)n * (maxlen + 2));
-    if (e == hipSuccess) e = W.ensure(9, rec_bytes);
-    if (e == hipSuccess) e = W.ensure_host(std::max(std::max(in_bytes, up256(ctl_bytes) + 256), rec_bytes));
-    GB_HIP(e);
+    int st = W.ensure(3, in_bytes);
+    if (!st) st = W.ensure(6, rec_bytes);
+    if (!st) st = W.ensure(7, ctl_bytes);
+    if (!st) st = W.ensure(8, sizeof(TEnt) * (size_t)n * (maxlen + 2));
+    if (!st) st = W.ensure(9, rec_bytes);
+    if (!st) st = W.ensure_host(std::max(std::max(in_bytes, up256(ctl_bytes) + 256), rec_bytes));
+    if (st) return st;
     uint8_t *h = W.h;
     std::memset(h, 0, 8);
     auto *hrid = reinterpret_cast<int32_t *>(h + i_rid);
@@ -551,20 +528,20 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
       hintv[i] = T.intv[todo[i]];
       hqpos[i] = mode == kOnePos ? T.qpos[todo[i]] : 0;
     }
-    uint8_t *din = (uint8_t *)W.buf[3], *dctl = (uint8_t *)W.buf[7];
+    uint8_t *din = (uint8_t *)W.buf[3].get(), *dctl = (uint8_t *)W.buf[7].get();
     GB_HIP(hipMemcpyAsync(din, h, in_bytes, hipMemcpyHostToDevice, s));
     A.cursor = (unsigned long long *)din;
     A.rid = (const int32_t *)(din + i_rid);
     A.intv = (const int32_t *)(din + i_intv);
     A.qpos = (const int16_t *)(din + i_qpos);
-    A.out = (TSmem *)W.buf[6];
-    A.compact = (TSmem *)W.buf[9];
+    A.out = (TSmem *)W.buf[6].get();
+    A.compact = (TSmem *)W.buf[9].get();
     A.counts = (int32_t *)dctl;
     A.rounds = (int32_t *)(dctl + c_rounds);
     A.tcalls = (uint32_t *)(dctl + c_tcalls);
     A.toff = (int32_t *)(dctl + c_toff);
     A.next_pos = (int16_t *)(dctl + c_np);
-    A.prev = (TEnt *)W.buf[8];
+    A.prev = (TEnt *)W.buf[8].get();
     A.ntasks = n;
     A.cap = cap;
     // a wave per task when the reads fit its LDS lists (GB_FMI_TASK_WAVE=0: a lane per task)
@@ -829,8 +806,8 @@ int gb_fmi_sa_raw(gb_fmi_index *idx, const int64_t *pos, int64_t n, int64_t *out
   GB_HIP(hipSetDevice(idx->device));
   Workspace &W = workspace(idx->device);
   if (!W.stream) GB_HIP(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-  GB_HIP(W.ensure(3, sizeof(int64_t) * 2 * (size_t)n));
-  int64_t *d = (int64_t *)W.buf[3];
+  if (int st = W.ensure(3, sizeof(int64_t) * 2 * (size_t)n)) return st;
+  int64_t *d = (int64_t *)W.buf[3].get();
   GB_HIP(hipMemcpyAsync(d, pos, sizeof(int64_t) * n, hipMemcpyHostToDevice, W.stream));
   hipLaunchKernelGGL(sa_raw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, W.stream, idx->d_sa, d, n, d + n);
   GB_HIP(hipGetLastError());
@@ -845,12 +822,12 @@ int gb_fmi_sa_one_step(gb_fmi_index *idx, int64_t pos, int64_t *sa_entry, int64_
   GB_HIP(hipSetDevice(idx->device));
   Workspace &W = workspace(idx->device);
   if (!W.stream) GB_HIP(hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-  GB_HIP(W.ensure(9, 4 * sizeof(int64_t)));
+  if (int st = W.ensure(9, 4 * sizeof(int64_t))) return st;
   DevIndex F;
   F.occ = nullptr;
   for (int b = 0; b < 5; b++) F.count[b] = idx->count[b];
   F.sentinel = idx->sentinel;
-  int64_t *d = (int64_t *)W.buf[9];
+  int64_t *d = (int64_t *)W.buf[9].get();
   hipLaunchKernelGGL(sa_one_step_kernel, dim3(1), dim3(1), 0, W.stream, idx->d_occ, idx->d_sa, F, pos, *offset, d);
   GB_HIP(hipGetLastError());
   int64_t r[3];

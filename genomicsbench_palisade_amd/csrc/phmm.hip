@@ -938,6 +938,9 @@ int ensure_host_tables() {
   return GB_OK;
 }
 
+// The device tables live as long as the process and are shared by every batch and thread, behind
+// g_mu: raw pointers that are never freed (a free at process exit could run after the HIP runtime
+// is torn down, and an owning buffer may not have static storage duration).
 template <typename T>
 int upload_tables(const HostTables<T> &h, T **dst) {
   const size_t nel = 3 * kQualTab + kM2M;
@@ -1022,11 +1025,10 @@ struct gb_phmm_batch {
   int n = 0;
   int max_haplen = 0;
   int64_t cells = 0;
-  uint8_t *h_stage = nullptr;  // pinned upload staging (grow-only)
-  size_t cap_stage = 0;
-  void *d_arena = nullptr;  // holds d_desc, d_rf, d_rd, d_out, d_stk_tc, d_stacks
+  gb::PinnedBuf<uint8_t> h_stage;  // upload staging (grow-only)
+  gb::DevBuf<uint8_t> d_arena;     // holds d_desc, d_rf, d_rd, d_out, d_stk_tc, d_stacks, d_units, d_ukey
   TcDesc *d_desc = nullptr;
-  uint8_t *d_pool = nullptr;
+  gb::DevBuf<uint8_t> d_pool;
   float *d_rf = nullptr;
   double *d_rd = nullptr;
   double *d_out = nullptr;
@@ -1035,15 +1037,14 @@ struct gb_phmm_batch {
   int nstacks = 0;                 // stacks whose haplotype fits the LDS (the first nstacks)
   int n_long = 0;                  // stacks behind them whose haplotype does not (kLong kernels)
   int long_grid = 0;               // their persistent grid
-  uint8_t *d_scratch = nullptr;    // their boundary records, scratch_stride bytes per workgroup
-  size_t scratch_stride = 0, cap_scratch = 0;
-  int *d_count = nullptr;  // [0] testcases recomputed by the f64 pass, [1] its stack counter,
+  gb::DevBuf<uint8_t> d_scratch;   // their boundary records, scratch_stride bytes per workgroup
+  size_t scratch_stride = 0;
+  gb::DevBuf<int> d_count;  // [0] testcases recomputed by the f64 pass, [1] its stack counter,
                            // [4..7] the f32 early exit's two u64 counts (testcases, cells skipped),
                            // [2] / [3] the kLong f32 / f64 stack counters, then the f64 plan's words
                            // (kCountWords in all)
   uint32_t *d_units = nullptr;  // f64 plan: units with work, costliest first (kMaxF64Parts per testcase)
   uint8_t *d_ukey = nullptr;    // f64 plan: per unit its cost bucket
-  size_t cap_n = 0, cap_pool = 0;  // allocated capacities (a cached workspace batch is refilled)
   int f64_grid = 0;                // persistent f64 grid: resident workgroups of the device
   int cus = 256;                   // compute units of the device (stack height rule)
   bool ran = false;
@@ -1095,10 +1096,15 @@ struct HostClock {
 // the old one, and hipFree waits for the device.
 int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
   const size_t nn = std::max(n, 1);
-  if (nn > b->cap_n) {
-    // the six per-testcase arrays carved from one allocation (a cold process pays per hipMalloc)
-    (void)hipFree(b->d_arena);
-    b->d_arena = nullptr;
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t sz[8] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
+                        up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
+                        up(sizeof(Stack) * nn),  // at most one stack per testcase
+                        up(sizeof(uint32_t) * nn * kMaxF64Parts), up(nn * kMaxF64Parts)};
+  const size_t arena = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6] + sz[7];
+  // every sz[] grows with nn, so an arena that holds this sum was carved for at least these sizes
+  if (arena > b->d_arena.capacity()) {
+    // the per-testcase arrays carved from one allocation (a cold process pays per hipMalloc)
     b->d_desc = nullptr;
     b->d_rf = nullptr;
     b->d_rd = b->d_out = nullptr;
@@ -1106,14 +1112,8 @@ int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
     b->d_stacks = nullptr;
     b->d_units = nullptr;
     b->d_ukey = nullptr;
-    b->cap_n = 0;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t sz[8] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
-                          up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
-                          up(sizeof(Stack) * nn),  // at most one stack per testcase
-                          up(sizeof(uint32_t) * nn * kMaxF64Parts), up(nn * kMaxF64Parts)};
-    GB_HIP(hipMalloc(&b->d_arena, sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6] + sz[7]));
-    uint8_t *a = (uint8_t *)b->d_arena;
+    if (int st = b->d_arena.reserve(arena)) return st;
+    uint8_t *a = b->d_arena;
     b->d_desc = (TcDesc *)a;
     a += sz[0];
     b->d_rf = (float *)a;
@@ -1129,30 +1129,18 @@ int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
     b->d_units = (uint32_t *)a;
     a += sz[6];
     b->d_ukey = a;
-    b->cap_n = nn;
   }
-  if (pool_bytes > b->cap_pool) {
-    (void)hipFree(b->d_pool);
-    b->d_pool = nullptr;
-    b->cap_pool = 0;
-    GB_HIP(hipMalloc(&b->d_pool, pool_bytes));
-    b->cap_pool = pool_bytes;
-  }
-  if (!b->d_count) GB_HIP(hipMalloc(&b->d_count, kCountWords * sizeof(int)));
-  return GB_OK;
+  if (int st = b->d_pool.reserve(pool_bytes)) return st;
+  return b->d_count.reserve(kCountWords);
 }
 
 // grow-only pinned staging buffer of a batch (uploads, results); its first `keep` bytes survive a growth
 int stage_reserve(gb_phmm_batch *b, size_t bytes, size_t keep = 0) {
-  if (bytes <= b->cap_stage) return GB_OK;
-  uint8_t *h = nullptr;
-  GB_HIP(hipHostMalloc((void **)&h, bytes, hipHostMallocDefault));
-  if (b->h_stage) {
-    if (keep) std::memcpy(h, b->h_stage, std::min(keep, b->cap_stage));
-    (void)hipHostFree(b->h_stage);
-  }
-  b->h_stage = h;
-  b->cap_stage = bytes;
+  if (bytes <= b->h_stage.capacity()) return GB_OK;
+  gb::PinnedBuf<uint8_t> h;
+  if (int st = h.reserve(bytes)) return st;
+  if (keep && b->h_stage) std::memcpy(h, b->h_stage, std::min(keep, b->h_stage.capacity()));
+  b->h_stage = std::move(h);
   return GB_OK;
 }
 
@@ -1230,7 +1218,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   host_reserve(b, nn, 0, nth);
   // descriptors are written by the pack (a bigger pool than guessed grows the buffer after it)
   if (int st = stage_reserve(b, StageLayout(nn, 32 * nn).total)) return st;
-  TcDesc *desc = (TcDesc *)b->h_stage;
+  TcDesc *desc = (TcDesc *)b->h_stage.get();
   uint32_t *hid = b->hid.data();  // dense haplotype index of each testcase (stack grouping)
   struct Chunk {
     int lo = 0, hi = 0;
@@ -1330,7 +1318,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   const size_t pool_bytes = std::max<size_t>((base[nth] + 15) & ~size_t(15), 16);
   const StageLayout L(nn, pool_bytes);
   if (int st = stage_reserve(b, L.total, sizeof(TcDesc) * nn)) return st;
-  desc = (TcDesc *)b->h_stage;
+  desc = (TcDesc *)b->h_stage.get();
   uint8_t *h_pool = b->h_stage + L.o_pool;
   std::vector<uint32_t> hap_off_of;
   std::vector<std::vector<uint32_t>> gid(nth);
@@ -1519,13 +1507,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     b->scratch_stride = (sizeof(Brec<double>) * (size_t)(max_h_long + kBndPad + kRecPad) +
                          (size_t)(max_h_long + kBndPad + kWave) + 16 + 255) & ~(size_t)255;
     const size_t need = b->scratch_stride * (size_t)b->long_grid;
-    if (need > b->cap_scratch) {
-      (void)hipFree(b->d_scratch);
-      b->d_scratch = nullptr;
-      b->cap_scratch = 0;
-      GB_HIP(hipMalloc(&b->d_scratch, need));
-      b->cap_scratch = need;
-    }
+    if (int st = b->d_scratch.reserve(need)) return st;
   }
   // the uploads go through the pinned staging buffer: a pageable copy is staged by the runtime, and
   // while an earlier chunk's kernels held the GPU one chunk's upload waited 10-15 ms for it
@@ -1830,11 +1812,11 @@ int gb_phmm_batch_results(gb_phmm_batch *b, double *results, float *raw_f, doubl
   const float *rf;
   const double *rd;
   const size_t off_d = (sizeof(float) * (size_t)n + 255) & ~(size_t)255;
-  if (b->h_stage && b->cap_stage >= off_d + sizeof(double) * (size_t)n) {
+  if (b->h_stage && b->h_stage.capacity() >= off_d + sizeof(double) * (size_t)n) {
     GB_HIP(hipMemcpyAsync(b->h_stage, b->d_rf, sizeof(float) * n, hipMemcpyDeviceToHost, b->stream));
     GB_HIP(hipMemcpyAsync(b->h_stage + off_d, b->d_rd, sizeof(double) * n, hipMemcpyDeviceToHost, b->stream));
     GB_HIP(hipStreamSynchronize(b->stream));
-    rf = (const float *)b->h_stage;
+    rf = (const float *)b->h_stage.get();
     rd = (const double *)(b->h_stage + off_d);
   } else {
     rf_v.resize(n);
@@ -1911,11 +1893,6 @@ int gb_phmm_batch_exit_stats(gb_phmm_batch *b, int64_t *dropped, int64_t *cells_
 int gb_phmm_batch_destroy(gb_phmm_batch *b) {
   if (!b) return GB_OK;
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  (void)hipFree(b->d_arena);
-  (void)hipFree(b->d_pool);
-  if (b->h_stage) (void)hipHostFree(b->h_stage);
-  (void)hipFree(b->d_count);
-  (void)hipFree(b->d_scratch);
   for (auto e : b->ev)
     if (e) (void)hipEventDestroy(e);
   if (b->stream) (void)hipStreamDestroy(b->stream);

@@ -283,3 +283,30 @@ def test_gpu_split_row_target(target, segmin, fault, monkeypatch):
         if fault:
             assert fixups > 0 and rounds > 1
     b.close()
+
+
+@pytest.mark.gpu
+def test_gpu_one_shot_refill_grow_shrink_grow(monkeypatch):
+    """gb_chain, the one-shot entry behind host_chain_kernel, keeps one batch per (thread, device) and
+    refills it: four calls in a row on this thread -- small whole calls, a set whose 3 000-anchor
+    cloud creates every split buffer, the small set again (every buffer larger than needed), and a
+    6 000-anchor cloud that grows every split buffer -- each bit-exact against the oracle."""
+    import ctypes
+    from genomicsbench_palisade_amd import check, lib, set_device
+    set_device(0)
+    L = lib()
+    rng = np.random.default_rng(17)
+    small = dict(num_calls=20, median_n=200, max_n=1000)
+    A = gen.chain_dataset("small", num_calls=40, median_n=200, max_n=1000)
+    B = _concat_calls([gen.chain_dataset("small", seed=3, **small), _cloud_call(rng, 3000, 4, 300, (1, 6), 3)])
+    C = _concat_calls([gen.chain_dataset("small", seed=4, **small), _cloud_call(rng, 6000, 4, 300, (1, 6), 3)])
+    exp = {id(c): oracle_lib.chain_oracle(c, 8) for c in (A, B, C)}
+    monkeypatch.setenv("GB_CHAIN_TARGET", "0")  # equal segments of GB_CHAIN_SPLIT's length
+    vp = ctypes.c_void_p
+    for calls, split in ((A, "0"), (B, "64,0"), (A, "0"), (C, "64,0")):
+        monkeypatch.setenv("GB_CHAIN_SPLIT", split)
+        outs = [np.full(calls.nanchors, -7, np.int32) for _ in range(4)]
+        check(L.gb_chain(ctypes.c_int64(calls.ncalls), vp(calls.offsets.ctypes.data), vp(calls.avg_qspan.ctypes.data),
+                         vp(calls.params4.ctypes.data), vp(calls.x.ctypes.data), vp(calls.y.ctypes.data),
+                         *[vp(o.ctypes.data) for o in outs]), "gb_chain")
+        assert_same(outs, exp[id(calls)])

@@ -381,3 +381,39 @@ def test_gpu_index_build_refuses_oversized_chunk_groups(fmi, monkeypatch):
     from genomicsbench_palisade_amd import GbError
     with pytest.raises(GbError, match="share one 8-base prefix"):
         fmi.Index.build(_repeat_heavy_reference())
+
+
+def test_recycled_read_set_and_workspace_grow_shrink_grow(fmi):
+    """A closed read set goes back to its thread's free list and the next one takes over its stream
+    and grow-only buffers; FMI_search's methods keep one workspace per (thread, device). Three sets in
+    a row on this thread -- small, large (every buffer grows), small again (every buffer larger than
+    needed) -- each searched and located, then each through getSMEMs: SMEMs, per-batch counts and SA
+    coordinates equal the oracle's every time."""
+    ref = gen.fmi_reference(30_000, seed=43)
+    sets = [gen.fmi_reads(ref, 100, read_len=60, seed=71, sub_rate=0.02),
+            gen.fmi_reads(ref, 2000, read_len=151, seed=72, sub_rate=0.02, n_rate=0.002)]
+    sets.append(sets[0])
+    oi = fmi_util.OracleIndex(ref)
+    idx = fmi.Index.build(ref)
+    for codes, lens in sets:
+        exp, ebc, epc = oi.run(codes, lens, batch_size=512)
+        exp_c, exp_n = oi.sa_entries(exp, max_occ=500, mode=1)
+        rs = fmi.Reads(idx, codes, lens)
+        rs.search(19)
+        sm, tot, bc, pc = rs.results(batch_size=512)
+        assert tot == len(exp) and (bc == ebc).all() and (pc == epc).all()
+        assert (smem_tuple_array(sm) == smem_tuple_array(exp)).all()
+        rs.sa_run(max_occ=500, mode=1)
+        c, n, ctot = rs.sa_results()
+        assert ctot == len(exp_c) and (n == exp_n).all() and (c == exp_c).all()
+        rs.close()
+    for codes, lens in sets:
+        c0 = oi.bwt_calls()
+        exp = oi.get_smems(codes, len(codes), 19, 1)
+        ecalls = oi.bwt_calls() - c0
+        got, calls = idx.get_smems(codes, len(codes), 19, 1)
+        assert len(exp) > 0 and len(got) == len(exp)
+        assert (smem_tuple_array(got) == smem_tuple_array(exp)).all()
+        assert calls == ecalls
+    idx.close()
+    oi.close()
