@@ -239,3 +239,73 @@ def global_band(len2, len1, w_cap=100, params=None):
 def cigar_string(ops):
     """'30M1D29M' for an array of len << 4 | op."""
     return "".join(f"{int(o) >> 4}{CIGAR_OPS[int(o) & 15]}" for o in ops)
+
+
+# ---- unbanded local alignment with sub-optimal score and start (ksw_align2, tools/bwa/ksw.c:63-365) ----
+
+# gb_bsw_lpair (include/gb_bsw.h), 56 bytes
+LPAIR_DTYPE = np.dtype([("idr", "<i8"), ("idq", "<i8"), ("len1", "<i4"), ("len2", "<i4"), ("xtra", "<i4"),
+                        ("score", "<i4"), ("te", "<i4"), ("qe", "<i4"), ("score2", "<i4"), ("te2", "<i4"),
+                        ("tb", "<i4"), ("qb", "<i4")])
+assert LPAIR_DTYPE.itemsize == 56
+LOCAL_FIELDS = ("score", "te", "qe", "score2", "te2", "tb", "qb")  # kswr_t's order
+LOCAL_MAX_TLEN = 16383
+# tools/bwa/ksw.h:6-9; the low 16 bits of xtra are the XSUBO / XSTOP threshold
+KSW_XBYTE, KSW_XSTOP, KSW_XSUBO, KSW_XSTART = 0x10000, 0x20000, 0x40000, 0x80000
+
+
+def _decl_local():
+    L = _decl()
+    if getattr(L, "_bsw_local_decl", False):
+        return L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.gb_bsw_local.argtypes = [vp, vp, i64, vp, i64, vp, i64]
+    L.gb_bsw_local_xtra.argtypes = [vp, i32, i32]
+    L.gb_bsw_local_timing.argtypes = [vp]
+    L._bsw_local_decl = True
+    return L
+
+
+def lpairs(pairs, xtra):
+    """gb_bsw_lpair records for a BswPairs set; xtra is one value or one per pair."""
+    lp = np.zeros(pairs.n, LPAIR_DTYPE)
+    lp["idr"], lp["idq"] = pairs.toff, pairs.qoff
+    lp["len1"], lp["len2"] = pairs.tlen, pairs.qlen
+    lp["xtra"] = xtra
+    for f in LOCAL_FIELDS:
+        lp[f] = -1
+    return lp
+
+
+def local_align(pairs, xtra, params=None):
+    """ksw_align2 for every pair of a BswPairs set (h0 is ignored) under xtra = KSW_X* flags |
+    threshold (scalar or per pair): (score, te, qe, score2, te2, tb, qb) as int32 arrays."""
+    params = params if params is not None else default_params()
+    lp = lpairs(pairs, xtra)
+    check(_decl_local().gb_bsw_local(ctypes.byref(params), _buf(lp), pairs.n, _buf(pairs.tgt), len(pairs.tgt),
+                                     _buf(pairs.qry), len(pairs.qry)), "gb_bsw_local")
+    return tuple(lp[f].copy() for f in LOCAL_FIELDS)
+
+
+def local_xtra(len2, min_seed_len=19, params=None):
+    """mem_matesw's xtra (bwamem_pair.c:150) for a mate of len2 bases: XSUBO | XSTART | (len2 * a < 250
+    ? XBYTE : 0) | min_seed_len * a with a = mat[0]. A scalar gives an int, an array an int32 array."""
+    params = params if params is not None else default_params()
+    L = _decl_local()
+
+    def one(q):
+        x = L.gb_bsw_local_xtra(ctypes.byref(params), int(q), int(min_seed_len))
+        check(min(x, 0), "gb_bsw_local_xtra")
+        return x
+    if np.ndim(len2) == 0:
+        return one(len2)
+    q = np.asarray(len2)
+    uniq, inv = np.unique(q, return_inverse=True)
+    return np.array([one(k) for k in uniq.tolist()], np.int32)[inv].reshape(q.shape)
+
+
+def local_timing():
+    """Kernel ms of this thread's last local_align, summed over its chunks."""
+    a = ctypes.c_float()
+    check(_decl_local().gb_bsw_local_timing(ctypes.byref(a)), "gb_bsw_local_timing")
+    return a.value

@@ -13,6 +13,11 @@
 // line of each pair record is then read as the band half-width w instead of h0, and one line per
 // pair, score NM CIGAR (tab separated), goes to the -o file, or to stdout when there is none (the
 // informational lines then go to stderr).
+// -local runs the mate-rescue step instead: the unbanded local alignment of each query against its
+// target (gb_bsw_local == bwa's ksw_align2). The first line of each pair record is then read as xtra
+// (KSW_X* flags | threshold, in decimal), targets may be up to 16383 bases long, and one line per
+// pair, score te qe score2 te2 tb qb (tab separated), goes to the -o file or to stdout as for
+// -global. -local and -global exclude each other.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,10 +30,10 @@
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
   const char *pair_file = nullptr, *out_file = nullptr;
-  bool global = false;
+  bool global = false, local = false;
   for (int i = 1; i < argc; i += 2) {
-    if (!strcmp(argv[i], "-global")) {  // the only flag without a value
-      global = true;
+    if (!strcmp(argv[i], "-global") || !strcmp(argv[i], "-local")) {  // the two flags without a value
+      (argv[i][1] == 'g' ? global : local) = true;
       --i;
       continue;
     }
@@ -49,6 +54,11 @@ int main(int argc, char **argv) {
     fprintf(stderr, "usage: bsw -pairs <InSeqFile> -t <threads> -b <batch_size>\n");
     return 1;
   }
+  if (global && local) {
+    fprintf(stderr, "bsw: -local and -global exclude each other\n");
+    return 1;
+  }
+  const size_t max_tlen = local ? GB_BSW_LOCAL_MAX_TLEN : 2047;
   FILE *f = fopen(pair_file, "r");
   if (!f) {
     fprintf(stderr, "Could not open file: %s\n", pair_file);
@@ -74,9 +84,9 @@ int main(int argc, char **argv) {
       fprintf(stderr, "WARNING! Odd number of sequences in %s\n", pair_file);
       break;
     }
-    if (r.empty() || q.empty() || r.size() > 2047 || q.size() > 255) {
-      fprintf(stderr, "pair %zu: target length %zu / query length %zu outside [1,2047] / [1,255]\n",
-              pairs.size(), r.size(), q.size());
+    if (r.empty() || q.empty() || r.size() > max_tlen || q.size() > 255) {
+      fprintf(stderr, "pair %zu: target length %zu / query length %zu outside [1,%zu] / [1,255]\n",
+              pairs.size(), r.size(), q.size(), max_tlen);
       return 1;
     }
     SeqPair sp;
@@ -95,7 +105,7 @@ int main(int argc, char **argv) {
   }
   fclose(f);
   const double read_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count();
-  FILE *info = global && !out_file ? stderr : stdout;
+  FILE *info = (global || local) && !out_file ? stderr : stdout;
   fprintf(info, "Number of input pairs: %zu\n", pairs.size());
   fprintf(info, "Read time = %0.2lf s\n", read_s);
 
@@ -146,6 +156,43 @@ int main(int argc, char **argv) {
       }
       fputc('\n', o);
     }
+    if (out_file) fclose(o);
+    return 0;
+  }
+  if (local) {
+    gb_bsw_params lp;
+    gb_bsw_default_params(&lp);
+    lp.o_del = lp.o_ins = w_open;
+    lp.e_del = lp.e_ins = w_extend;
+    memcpy(lp.mat, mat, sizeof(mat));
+    std::vector<gb_bsw_lpair> lpairs(pairs.size());
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      gb_bsw_lpair &l = lpairs[k];
+      memset(&l, 0, sizeof(l));
+      l.idr = pairs[k].idr;
+      l.idq = pairs[k].idq;
+      l.len1 = pairs[k].len1;
+      l.len2 = pairs[k].len2;
+      l.xtra = pairs[k].h0;  // the record's first line
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int st = gb_bsw_local(&lp, lpairs.data(), (int64_t)lpairs.size(), ref.data(), (int64_t)ref.size(), qer.data(),
+                                (int64_t)qer.size());
+    const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (st) {
+      fprintf(stderr, "gb_bsw_local failed (%d): %s\n", st, gb_last_error());
+      return 1;
+    }
+    fprintf(info, "Executed MI355X local alignment (gfx950)...\n");
+    fprintf(info, "Overall alignment time = %0.3f s (incl. host<->device copies)\n", sw_s);
+    fprintf(info, "Total Pairs processed: %zu\n", pairs.size());
+    FILE *o = out_file ? fopen(out_file, "w") : stdout;
+    if (!o) {
+      fprintf(stderr, "Could not open file: %s\n", out_file);
+      return 1;
+    }
+    for (const auto &l : lpairs)
+      fprintf(o, "%d\t%d\t%d\t%d\t%d\t%d\t%d\n", l.score, l.te, l.qe, l.score2, l.te2, l.tb, l.qb);
     if (out_file) fclose(o);
     return 0;
   }

@@ -128,6 +128,53 @@ int gb_bsw_global_band(const gb_bsw_params *params, int32_t len2, int32_t len1, 
  * chunks: the DP fill kernel and the traceback kernel (0 for a scores-only call). */
 int gb_bsw_global_timing(float *fill_ms, float *walk_ms);
 
+/* ---- unbanded local alignment with sub-optimal score and start: bwa's ksw_align2 (tools/bwa/ksw.c:
+ * 63-365), the call mem_matesw makes for mate rescue (tools/bwa/bwamem_pair.c:150-151). Per pair the
+ * seven fields of kswr_t, each bit for bit what ksw_align2(len2, query, len1, target, 5, mat, o_del,
+ * e_del, o_ins, e_ins, xtra, 0) returns: score, te, qe (best local score and the target / query
+ * positions where it ends), score2, te2 (the best row maximum >= xtra & 0xffff that ends more than
+ * ceil(score / max(mat)) rows away from te; -1, -1 without GB_KSW_XSUBO or when there is none) and tb,
+ * qb (where the best alignment starts; -1, -1 without GB_KSW_XSTART or when score lies below the
+ * GB_KSW_XSUBO threshold). The reference pads the query with columns that score 0 up to a multiple of
+ * 16 (GB_KSW_XBYTE) or 8; those columns take part in the row maxima behind score2 / te2, and they do
+ * here. One more property of the reference is reproduced: with o_ins == 0 its lazy-F loop ends after
+ * the first step, so an insertion no longer crosses more than one boundary between the p stripes of
+ * L/p query columns, and scores can lie below the ordinary DP's ("bsw (local)").
+ *
+ * Accepted domain, per pair: 1 <= len2 <= GB_BSW_MAX_QLEN, 1 <= len1 <= GB_BSW_LOCAL_MAX_TLEN, offsets
+ * inside the sequence buffers, no bit of xtra above bit 15 other than the four GB_KSW_X* flags;
+ * max(mat) >= 1 and min(mat) <= 0; o_del, e_del, o_ins, e_ins >= 0 with o_del + e_del < 32768 and
+ * o_ins + e_ins < 32768. With GB_KSW_XBYTE additionally o_del + e_del <= 255, o_ins + e_ins <= 255
+ * (the reference truncates them to a byte) and len2 * max(mat) - min(mat) < 255, so that the
+ * reference's byte kernel cannot saturate (bwa's own rule, len2 * a < 250, lies inside this). Anything
+ * else fails the whole call with GB_ERR_ARG before any device work, nothing is written, and
+ * gb_last_error() names the pair. params->zdrop, end_bonus and w are ignored. */
+#define GB_KSW_XBYTE 0x10000  /* tools/bwa/ksw.h:6-9 */
+#define GB_KSW_XSTOP 0x20000  /* stop once score >= xtra & 0xffff */
+#define GB_KSW_XSUBO 0x40000  /* track score2 / te2 among row maxima >= xtra & 0xffff */
+#define GB_KSW_XSTART 0x80000 /* find tb / qb */
+#define GB_BSW_LOCAL_MAX_TLEN 16383 /* bwa caps the insert size that bounds a mate-rescue window at 10 000 */
+
+typedef struct gb_bsw_lpair { /* 56 bytes */
+  int64_t idr, idq;           /* target / query offsets, as in gb_seqpair */
+  int32_t len1, len2, xtra;   /* target, query length; GB_KSW_X* flags | threshold */
+  int32_t score, te, qe, score2, te2, tb, qb; /* out */
+} gb_bsw_lpair;
+
+/* num_pairs == 0 succeeds without a device. Device and pinned buffers are cached per (calling
+ * thread, device); a large call runs in chunks of pairs. */
+int gb_bsw_local(const gb_bsw_params *params, gb_bsw_lpair *pairs, int64_t num_pairs,
+                 const uint8_t *seq_buf_ref, int64_t ref_bytes, const uint8_t *seq_buf_qer,
+                 int64_t qer_bytes);
+
+/* mem_matesw's xtra (bwamem_pair.c:150) for a mate of len2 bases with a = params->mat[0]:
+ * XSUBO | XSTART | (len2 * a < 250 ? XBYTE : 0) | (min_seed_len * a). GB_ERR_ARG (negative) when
+ * min_seed_len * a does not fit the 16 threshold bits. */
+int gb_bsw_local_xtra(const gb_bsw_params *params, int32_t len2, int32_t min_seed_len);
+
+/* Device time of the calling thread's last gb_bsw_local on the current device, summed over its chunks. */
+int gb_bsw_local_timing(float *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
