@@ -30,6 +30,7 @@
 #include <cstring>
 #include <functional>
 #include <future>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -139,11 +140,39 @@ static uint8_t base_code(char ch) {
 // either is N (mask construction in avx-pairhmm-template.h:5-27).
 static uint8_t read_match_mask(uint8_t rc) { return rc == 4 ? 0x1F : (uint8_t)((1u << rc) | 0x10); }
 
+// The early exit's gate (phmm_stack, "Early exit"). exit_growth: G >= prod_k max(1, g_k) over the rows
+// k of a packed read (rmatch[R] q[R] i[R] d[R] c[R]) that have a row below them, g_k the most the
+// crossing mass can grow from the crossing into row k to the crossing out of it, whatever the
+// haplotype; from the f32 table values the kernel multiplies by, in double. +inf when a row's gap
+// mass does not decay (ph2pr[c_k] = 1: its geometric sum is the haplotype's length, which a read
+// shared between haplotypes does not know) yet leaks into the row below. A read may exit when
+// G <= kExitGrowthMax; the pack sets kMayExit in every row's match mask then.
+constexpr double kExitGrowthMax = 2.0;
+constexpr uint8_t kMayExit = 0x80;
+static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R) {
+  const double inf = std::numeric_limits<double>::infinity();
+  double G = 1.0;
+  for (int k = 0; k + 1 < R; k++) {
+    const int qd = rec[3 * R + k] & 127, qc = rec[4 * R + k] & 127;  // own row: pMY, pYY
+    const int ni = rec[2 * R + k + 1] & 127, nd = rec[3 * R + k + 1] & 127, nc = rec[4 * R + k + 1] & 127;
+    const int mn = std::min(ni, nd), mx = std::max(ni, nd);
+    const double nMM = t.m2m[((mx * (mx + 1)) >> 1) + mn], nMX = t.ph2pr[ni];
+    const double nGAPM = t.one_minus[nc], nXX = t.ph2pr[nc];
+    const double pYY = t.ph2pr[qc], leak = (double)t.ph2pr[qd] * nGAPM;
+    if (leak > 0 && pYY >= 1.0) return inf;
+    const double gM = nMM + nMX + (leak > 0 ? leak / (1.0 - pYY) : 0.0), gX = nGAPM + nXX;
+    const double g = std::max(gM, gX);
+    if (g > 1.0) G *= g;
+    if (G > 1e30) return inf;
+  }
+  return G;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Device side
 // ---------------------------------------------------------------------------------------------
 struct __attribute__((aligned(16))) TcDesc {
-  uint32_t read_off;  // pool offset: rmatch[R] q[R] i[R] d[R] c[R]
+  uint32_t read_off;  // pool offset: rmatch[R] (| kMayExit) q[R] i[R] d[R] c[R]
   uint32_t hap_off;   // pool offset: hcode[C]
   uint32_t dims;      // rslen | haplen << 16
   uint32_t out_idx;   // position in the caller's testcase array
@@ -515,14 +544,38 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
     __syncthreads();
     int next = base + kWave;
     if constexpr (!kF64Pass && kExit) {
-      // Early exit (GB_PHMM_EXIT): every path of a testcase crosses from its row r to row r+1 once,
-      // and what follows multiplies by transitions and emissions <= 1, so its result is at most the
-      // crossing mass sum_c (z + w) of row r -- the records lane 63 just wrote for the next stripe,
-      // already multiplied by row r+1's transitions. Below MIN_ACCEPTED / 4 (margin for the f32
-      // rounding of the sum and of the rows not computed) the testcase must fail the f32 test: its
-      // remaining rows are skipped, its f32 result is written as 0, and the f64 pass computes it as
-      // it would have anyway. Only rows with a row of the same testcase below them are tested.
-      if (r63 >= 2 && r63 <= R63) {
+      // Early exit (GB_PHMM_EXIT). Every path of a testcase crosses from its row r to row r+1 once. The
+      // crossing mass A_r = sum_c (z + w) of row r is what lane 63 just wrote for the next stripe,
+      // already multiplied by row r+1's transitions. Row r+1 takes M = z * dist and X = w from it, so
+      // its entering mass E = sum_c (M + X) is <= A_r (dist <= 1), and the result is the last row's E.
+      // In between the mass can GROW: every single transition is <= 1, a state's total outflow is
+      // not. Out of row k (its own pMY, pYY; row k+1's nMM, nMX, nGAPM, nXX) a unit of M sends
+      // nMM + nMX straight down and pMY into Y, which hands pMY * nGAPM * sum_{j<C} pYY^j down along
+      // the row; a unit of X sends nGAPM + nXX. So
+      //   A_k <= g_k * E_k,   g_k = max(nMM + nMX + pMY * nGAPM / (1 - pYY), nGAPM + nXX),
+      // and g_k > 1 on inputs the reference accepts:
+      //   * clamped pMM: GKL clamps 1 - (10^(-i/10) + 10^(-d/10)) at 0 and does not renormalise, so
+      //     for i, d of 0..3 nMM + nMX + pMY reaches 2;
+      //   * the Y leak: Y stays with row k's ph2pr[c_k] and leaves with 1 - ph2pr[c_{k+1}], which sum
+      //     to 1 only when c_k = c_{k+1}; with ph2pr[c_k] = 1 the geometric sum is C;
+      //   * pMY is row k's while nMM, nMX are row k+1's: 10^(-d_k/10) - 10^(-d_{k+1}/10) is left over
+      //     where the deletion quality falls from a row to the next (6.8e-5 a row for d of 40..45);
+      //   * the rounding of the f32 tables (5.1e-8 where pMM > 0).
+      // With G >= prod_k max(1, g_k) over the read's rows (exit_growth: the f32 table values used
+      // here, in double; +inf where unbounded), result <= A_r * G in exact arithmetic. In f32 every
+      // product and sum of these non-negative terms is at most its exact value times 1 + 2^-24, plus
+      // 2^-150 where it rounds into the denormals. A path takes at most 4 roundings through a row
+      // besides the Y chain's 2 per column, which act on the geometric sum like
+      // pYY * (1 + 2^-24)^2 <= 0.7944: < (1 + 2^-24)^15 a row, < 1.07 over 65535 rows; the last row's
+      // sums add (1 + 2^-24)^(C+1) < 1.004, this block's own sum < 1.0001; the denormal terms of a
+      // whole 65535 x 65535 matrix, 12 operations a cell, sum to < 4e-35, each growing by at most G
+      // afterwards. Hence the f32 result is < 1.08 * G * (A_r + 4e-35). The pack lets a read exit only
+      // when its G <= kExitGrowthMax = 2 (kMayExit in its rows' match masks; benchmark-range reads, i
+      // and d of 40..45 with one c, have G < 1.02 at 250 rows), so the test A_r < MIN_ACCEPTED / 4 gives
+      // a result < 2.16 * (0.25e-28 + 4e-35) < MIN_ACCEPTED: the testcase must fail the f32 test. Its
+      // remaining rows are skipped, its f32 result is written as 0, and the f64 pass computes it as it
+      // would have anyway. Only rows with a row of the same testcase below them are tested.
+      if (r63 >= 2 && r63 <= R63 && (__builtin_amdgcn_readlane((int)P.rmask, 63) & kMayExit)) {
         T acc = (T)0;
 #pragma unroll 1
         for (int c = 1 + lane; c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
@@ -1263,6 +1316,9 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
             rec[3 * t.rslen + r] = (uint8_t)t.d[r];
             rec[4 * t.rslen + r] = (uint8_t)t.c[r];
           }
+          // the early exit's gate: bit 7 of every row's match mask (select_dist reads bits 0..6)
+          if (exit_growth(b->tabs->hf, rec, t.rslen) <= kExitGrowthMax)
+            for (int r = 0; r < t.rslen; r++) rec[r] |= kMayExit;
           read_at.emplace(rk, roff);
         }
       }
