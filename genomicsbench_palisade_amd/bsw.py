@@ -6,6 +6,7 @@ Pairs are gen.BswPairs (flattened target/query buffers, SeqPair.idr/idq = offset
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 
@@ -309,3 +310,172 @@ def local_timing():
     a = ctypes.c_float()
     check(_decl_local().gb_bsw_local_timing(ctypes.byref(a)), "gb_bsw_local_timing")
     return a.value
+
+
+# ---- CIGAR, NM and MD from reference coordinates (bwa_gen_cigar2, tools/bwa/bwa.c:121-208) ----------
+
+# gb_bsw_cpair (include/gb_bsw.h), 64 bytes
+CPAIR_DTYPE = np.dtype([("rb", "<i8"), ("re", "<i8"), ("idq", "<i8"), ("len2", "<i4"), ("w", "<i4"), ("score", "<i4"),
+                        ("n_cigar", "<i4"), ("nm", "<i4"), ("md_len", "<i4"), ("cigar_off", "<i8"), ("md_off", "<i8")])
+assert CPAIR_DTYPE.itemsize == 64
+CIGAR_FIELDS = ("score", "n_cigar", "nm", "md_len", "cigar_off", "md_off")
+
+
+def _decl_gencigar():
+    L = _decl_global()
+    if getattr(L, "_bsw_gencigar_decl", False):
+        return L
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    L.gb_ref_create.argtypes = [vp, i64, ctypes.POINTER(vp)]
+    L.gb_ref_load_pac.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
+    L.gb_ref_info.argtypes = [vp, vp]
+    L.gb_ref_destroy.argtypes = [vp]
+    L.gb_ref_fetch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
+    L.gb_bsw_gen_cigar.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp]
+    L.gb_bsw_gen_cigar_retry.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp]
+    L.gb_bsw_gen_cigar_timing.argtypes = [vp, vp, vp, vp]
+    L._bsw_gencigar_decl = True
+    return L
+
+
+def pack_pac(codes):
+    """bwa's 2-bit packing of base codes 0..3: base l in byte l >> 2 at shift (~l & 3) << 1 (_set_pac,
+    tools/bwa/bntseq.c:42)."""
+    c = np.asarray(codes, np.uint8)
+    if len(c) < 1 or (c > 3).any():
+        raise ValueError("a packed reference holds at least one base, codes 0..3 only")
+    c4 = np.zeros((len(c) + 3) // 4 * 4, np.uint8)
+    c4[:len(c)] = c
+    c4 = c4.reshape(-1, 4)
+    return (c4[:, 0] << 6 | c4[:, 1] << 4 | c4[:, 2] << 2 | c4[:, 3]).astype(np.uint8)
+
+
+class Ref:
+    """gb_ref: a packed reference, uploaded to the current device by the first call that uses it."""
+
+    def __init__(self, handle):
+        self.h = handle
+        n = ctypes.c_int64()
+        check(_decl_gencigar().gb_ref_info(self.h, ctypes.byref(n)), "gb_ref_info")
+        self.l_pac = n.value
+
+    @classmethod
+    def from_pac(cls, pac, l_pac):
+        """From (l_pac + 3) // 4 packed bytes in bwa's layout."""
+        pac = np.ascontiguousarray(pac, np.uint8)
+        if len(pac) < (int(l_pac) + 3) // 4:
+            raise ValueError("pac is shorter than (l_pac + 3) // 4 bytes")
+        h = ctypes.c_void_p()
+        check(_decl_gencigar().gb_ref_create(pac.ctypes.data, int(l_pac), ctypes.byref(h)), "gb_ref_create")
+        return cls(h)
+
+    @classmethod
+    def from_codes(cls, codes):
+        """From base codes 0..3, one per byte (packed here with numpy)."""
+        return cls.from_pac(pack_pac(codes), len(codes))
+
+    @classmethod
+    def from_pac_file(cls, path):
+        """From a bwa .pac file."""
+        h = ctypes.c_void_p()
+        check(_decl_gencigar().gb_ref_load_pac(os.fsencode(path), ctypes.byref(h)), "gb_ref_load_pac")
+        return cls(h)
+
+    def fetch(self, beg, end):
+        """bns_get_seq for every region (beg[r], end[r]) of the doubled coordinate space: (bytes uint8,
+        off int64 [n], len int32 [n]); region r is bytes[off[r] : off[r] + len[r]]."""
+        beg = np.ascontiguousarray(np.atleast_1d(beg), np.int64)
+        end = np.ascontiguousarray(np.atleast_1d(end), np.int64)
+        n = len(beg)
+        off, ln = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+        # an upper bound on the total without repeating the clamps: |end - beg| per region
+        cap = int(np.minimum(np.abs(end - beg), 2 * self.l_pac).sum())
+        out = np.zeros(max(cap, 1), np.uint8)
+        check(_decl_gencigar().gb_ref_fetch(self.h, _buf(beg), _buf(end), n, out.ctypes.data, cap, off.ctypes.data,
+                                            ln.ctypes.data), "gb_ref_fetch")
+        return out[:int(ln[:n].sum())].copy(), off[:n], ln[:n]
+
+    def close(self):
+        if self.h:
+            _decl_gencigar().gb_ref_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cpairs(queries, rb, re, w):
+    """(gb_bsw_cpair records, flat query buffer) for a list of uint8 code arrays and their regions; w is
+    one value or one per pair. The out fields start at -1."""
+    n = len(queries)
+    cp = np.zeros(n, CPAIR_DTYPE)
+    ql = np.array([len(q) for q in queries], np.int64)
+    cp["rb"], cp["re"], cp["len2"], cp["w"] = rb, re, ql, w
+    cp["idq"] = np.concatenate([[0], np.cumsum(ql)[:-1]]) if n else 0
+    for f in CIGAR_FIELDS:
+        cp[f] = -1
+    qbuf = np.concatenate([np.asarray(q, np.uint8) for q in queries]) if n else np.zeros(0, np.uint8)
+    return cp, np.ascontiguousarray(qbuf)
+
+
+def md_cap(rb, re):
+    """GB_BSW_MD_CAP summed over the regions: the md capacity that always suffices."""
+    d = np.abs(np.asarray(re, np.int64) - np.asarray(rb, np.int64))
+    return int((3 * d + 1).sum())
+
+
+def _gen_cigar_call(fn, what, ref, queries, rb, re, w, params, want_cigar, want_md, truesc=None):
+    params = params if params is not None else default_params()
+    if want_md and not want_cigar:
+        raise ValueError("MD needs the CIGAR: want_md requires want_cigar")
+    cp, qbuf = cpairs(queries, rb, re, w)
+    d = np.abs(cp["re"] - cp["rb"])
+    ccap = int((d + cp["len2"]).sum()) if want_cigar else 0
+    mcap = md_cap(cp["rb"], cp["re"]) if want_md else 0
+    cigar, md = np.zeros(max(ccap, 1), np.uint32), np.zeros(max(mcap, 1), np.uint8)
+    cu, mu = ctypes.c_int64(0), ctypes.c_int64(0)
+    args = [ctypes.byref(params), ref.h, _buf(cp), len(cp), _buf(qbuf), len(qbuf)]
+    tries = None
+    if truesc is not None:
+        ts = np.ascontiguousarray(truesc, np.int32)
+        tries = np.zeros(max(len(cp), 1), np.int32)
+        args.append(_buf(ts))
+    args += [cigar.ctypes.data if want_cigar else None, ccap, ctypes.byref(cu),
+             md.ctypes.data if want_md else None, mcap, ctypes.byref(mu)]
+    if truesc is not None:
+        args.append(tries.ctypes.data)
+    check(fn(*args), what)
+    res = {f: cp[f].copy() for f in CIGAR_FIELDS}
+    res["w"] = cp["w"].copy()
+    res["cigar"] = cigar[:cu.value].copy()
+    res["md"] = md[:mu.value].tobytes()
+    if tries is not None:
+        res["tries"] = tries[:len(cp)]
+    return res
+
+
+def gen_cigar(ref, queries, rb, re, w, params=None, want_cigar=True, want_md=True):
+    """bwa_gen_cigar2 for every (query, region [rb, re) of ref's doubled coordinate space, w). Returns a
+    dict: score, n_cigar, nm, md_len, cigar_off, md_off (arrays, one entry per pair), cigar (uint32,
+    len << 4 | op) and md (bytes); pair p owns cigar[cigar_off[p] : cigar_off[p] + n_cigar[p]] and
+    md[md_off[p] : md_off[p] + md_len[p]]. A pair the reference rejects has n_cigar 0, nm -1, md_len 0
+    and score -1 (the value this wrapper starts from). want_cigar=False asks for scores only."""
+    return _gen_cigar_call(_decl_gencigar().gb_bsw_gen_cigar, "gb_bsw_gen_cigar", ref, queries, rb, re, w, params,
+                           want_cigar, want_md)
+
+
+def gen_cigar_retry(ref, queries, rb, re, w, truesc, params=None, want_cigar=True, want_md=True):
+    """gen_cigar inside mem_reg2aln's re-banding loop (tools/bwa/bwamem.c:1154-1163): the same dict plus
+    w (each pair's band argument on its last try) and tries."""
+    return _gen_cigar_call(_decl_gencigar().gb_bsw_gen_cigar_retry, "gb_bsw_gen_cigar_retry", ref, queries, rb, re, w,
+                           params, want_cigar, want_md, truesc=truesc)
+
+
+def gen_cigar_timing():
+    """(fetch_ms, fill_ms, walk_ms, md_ms): device time of this thread's last gen_cigar / gen_cigar_retry."""
+    t = [ctypes.c_float() for _ in range(4)]
+    check(_decl_gencigar().gb_bsw_gen_cigar_timing(*[ctypes.byref(x) for x in t]), "gb_bsw_gen_cigar_timing")
+    return tuple(x.value for x in t)

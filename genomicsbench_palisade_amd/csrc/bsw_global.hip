@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/gb_bsw.h"
+#include "bsw_global_internal.h"
 #include "gb_common.h"
 
 static_assert(sizeof(gb_bsw_gpair) == 48, "gb_bsw_gpair is 48 bytes (include/gb_bsw.h)");
@@ -38,18 +39,6 @@ constexpr int kNegInf = -0x40000000;  // MINUS_INF (ksw.c:490)
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlocksPerCU = 8;
 constexpr int kMaxPenalty = 32768;  // gap penalties lie in [0, kMaxPenalty)
-
-struct Pair {  // device descriptor, 40 B
-  int64_t t_off, q_off;
-  int64_t dir_off;  // first 16-bit word of this pair's direction matrix
-  int32_t tlen, qlen, w, pad;
-};
-
-__host__ __device__ inline int cols_per_lane(int qlen) { return (qlen + 64) >> 6; }  // columns 0..qlen
-__host__ __device__ inline int row_words(int qlen) {  // lanes owning a query column
-  const int K = cols_per_lane(qlen);
-  return (qlen + K - 1) / K;
-}
 
 struct FillArgs {
   const Pair *pairs;
@@ -322,19 +311,6 @@ int64_t dir_words_limit() {  // GB_BSW_GLOBAL_DIR_WORDS (tests: many chunks from
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kDirWords)) : kDirWords;
 }
 
-struct Ws {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
-  int device = -1, num_cus = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  gb::DevBuf<uint8_t> d_tgt, d_qry;
-  gb::DevBuf<Pair> d_pairs;
-  gb::DevBuf<int32_t> d_out4;
-  gb::DevBuf<uint16_t> d_dir;
-  gb::DevBuf<uint32_t> d_pool;
-  gb::DevBuf<unsigned int> d_ctl;  // [0] fill work counter, [1] pool operations used, [2] first clamped pair
-  float fill_ms = 0.f, walk_ms = 0.f;
-};
-
 thread_local std::vector<Ws *> g_ws;
 
 Ws *find_ws(int dev) {
@@ -432,7 +408,6 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
   if (st) return st;
   if (cigar_used) *cigar_used = 0;
   if (n == 0) return GB_OK;
-  const bool want = cigar != nullptr;
 
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
@@ -443,7 +418,20 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
   if ((st = W->d_qry.reserve((size_t)qer_bytes))) return st;
   GB_HIP(hipMemcpyAsync(W->d_tgt, ref, (size_t)ref_bytes, hipMemcpyHostToDevice, W->stream));
   GB_HIP(hipMemcpyAsync(W->d_qry, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, W->stream));
+  return run_resident(W, "gb_bsw_global", params, pairs, n, W->d_tgt, W->d_qry, cigar, cigar_cap, cigar_used,
+                      &W->fill_ms, &W->walk_ms, nullptr);
+}
 
+}  // extern "C"
+
+namespace gbbswg {
+
+int run_resident(Ws *W, const char *who, const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n,
+                 const uint8_t *d_tgt, const uint8_t *d_qry, uint32_t *cigar, int64_t cigar_cap, int64_t *cigar_used,
+                 float *fill_ms, float *walk_ms, ChunkHook *hook) {
+  int st = GB_OK;
+  if (cigar_used) *cigar_used = 0;
+  const bool want = cigar != nullptr;
   // Operations go straight into cigar[] when it holds the worst case; otherwise they are staged so
   // that cigar[] stays untouched should the total exceed cigar_cap.
   int64_t worst = 0;
@@ -482,8 +470,8 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
     FillArgs F;
     F.pairs = W->d_pairs;
     F.n = m;
-    F.tgt = W->d_tgt;
-    F.qry = W->d_qry;
+    F.tgt = d_tgt;
+    F.qry = d_qry;
     F.out4 = W->d_out4;
     F.dir = want ? W->d_dir.get() : nullptr;
     F.next = W->d_ctl;
@@ -506,8 +494,8 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
       WalkArgs A;
       A.pairs = W->d_pairs;
       A.n = m;
-      A.tgt = W->d_tgt;
-      A.qry = W->d_qry;
+      A.tgt = d_tgt;
+      A.qry = d_qry;
       A.out4 = W->d_out4;
       A.dir = W->d_dir;
       A.pool = W->d_pool;
@@ -517,6 +505,7 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
       GB_HIP(hipGetLastError());
     }
     GB_HIP(hipEventRecord(W->ev[2], W->stream));
+    if (want && hook && (st = hook->enqueue(W->stream, lo, m, W->d_pairs, W->d_out4, W->d_pool))) return st;
     o4.resize((size_t)m * 4);
     unsigned int ctl[4] = {0, 0, 0, 0};
     GB_HIP(hipMemcpyAsync(o4.data(), W->d_out4, (size_t)m * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, W->stream));
@@ -524,13 +513,13 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
     GB_HIP(hipStreamSynchronize(W->stream));
     float ms = 0.f;
     GB_HIP(hipEventElapsedTime(&ms, W->ev[0], W->ev[1]));
-    W->fill_ms += ms;
+    *fill_ms += ms;
     GB_HIP(hipEventElapsedTime(&ms, W->ev[1], W->ev[2]));
-    W->walk_ms += ms;
+    *walk_ms += ms;
     const int64_t used = want ? (int64_t)ctl[1] : 0;
     if (used > ops) {
-      gb::set_error("gb_bsw_global: the device reserved %lld operations for a chunk that can need at most %lld",
-                    (long long)used, (long long)ops);
+      gb::set_error("%s: the device reserved %lld operations for a chunk that can need at most %lld",
+                    who, (long long)used, (long long)ops);
       return GB_ERR_STATE;
     }
     if (want && ctl[2] != 0xFFFFFFFFu && bad_pair < 0) bad_pair = lo + (int64_t)ctl[2];
@@ -550,27 +539,28 @@ int gb_bsw_global(const gb_bsw_params *params, gb_bsw_gpair *pairs, int64_t n, c
       if (want) {
         const int64_t nc = o[1], off = (int64_t)(uint32_t)o[3];
         if (nc < 0 || off + nc > used) {
-          gb::set_error("gb_bsw_global: pair %lld reports %lld operations at pool offset %lld of %lld",
-                        (long long)(lo + k), (long long)nc, (long long)off, (long long)used);
+          gb::set_error("%s: pair %lld reports %lld operations at pool offset %lld of %lld",
+                        who, (long long)(lo + k), (long long)nc, (long long)off, (long long)used);
           return GB_ERR_STATE;
         }
         std::memcpy(dst + total, pool.data() + off, (size_t)nc * sizeof(uint32_t));
         total += nc;
       }
     }
+    if (want && hook && (st = hook->collect(lo, m))) return st;
     lo = hi;
   }
   if (cigar_used) *cigar_used = total;
   if (bad_pair >= 0) {
-    gb::set_error("gb_bsw_global: the traceback of pair %lld did not end within len1 + len2 steps", (long long)bad_pair);
+    gb::set_error("%s: the traceback of pair %lld did not end within len1 + len2 steps", who, (long long)bad_pair);
     return GB_ERR_STATE;
   }
   if (want && !direct) {
-    GB_ARG(total <= cigar_cap, "gb_bsw_global: cigar_cap %lld is below the %lld operations of this call",
+    GB_ARG(total <= cigar_cap, "%s: cigar_cap %lld is below the %lld operations of this call", who,
            (long long)cigar_cap, (long long)total);
     if (total) std::memcpy(cigar, staged.data(), (size_t)total * sizeof(uint32_t));
   }
   return GB_OK;
 }
 
-}  // extern "C"
+}  // namespace gbbswg

@@ -18,6 +18,12 @@
 // (KSW_X* flags | threshold, in decimal), targets may be up to 16383 bases long, and one line per
 // pair, score te qe score2 te2 tb qb (tab separated), goes to the -o file or to stdout as for
 // -global. -local and -global exclude each other.
+// -gencigar -pac <file.pac> takes reference coordinates instead of targets: all of bwa_gen_cigar2
+// (gb_bsw_gen_cigar) over the packed reference of a bwa index. A pair record is then two lines,
+// "rb re w" (the region in bwa's doubled coordinate space and bwa_gen_cigar2's w_ argument) and the
+// query. One line per pair, score NM CIGAR MD (tab separated), goes to the -o file or to stdout as for
+// -global; a pair the reference rejects prints * for CIGAR and MD. -gencigar excludes -global and
+// -local.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,13 +33,100 @@
 
 #include "../../include/gb_compat/bandedSWA.h"
 
+// -gencigar: records of two lines, "rb re w" and the query
+static int run_gencigar(const char *pac_file, const char *pair_file, const char *out_file, const gb_bsw_params &gp) {
+  gb_ref *ref = nullptr;
+  int st = gb_ref_load_pac(pac_file, &ref);
+  if (st) {
+    fprintf(stderr, "gb_ref_load_pac failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  FILE *f = fopen(pair_file, "r");
+  if (!f) {
+    fprintf(stderr, "Could not open file: %s\n", pair_file);
+    return 1;
+  }
+  std::vector<gb_bsw_cpair> pairs;
+  std::vector<uint8_t> qer;
+  std::vector<char> line(1 << 12);
+  size_t ccap = 0, mcap = 0;
+  while (fgets(line.data(), (int)line.size(), f)) {
+    gb_bsw_cpair c;
+    memset(&c, 0, sizeof(c));
+    long long rb = 0, re = 0;
+    int w = 0;
+    if (sscanf(line.data(), "%lld %lld %d", &rb, &re, &w) != 3) {
+      fprintf(stderr, "pair %zu: expected \"rb re w\"\n", pairs.size());
+      return 1;
+    }
+    if (!fgets(line.data(), (int)line.size(), f)) {
+      fprintf(stderr, "WARNING! A record without its query line in %s\n", pair_file);
+      break;
+    }
+    size_t n = strlen(line.data());
+    while (n && (line[n - 1] == '\n' || line[n - 1] == '\r')) --n;
+    if (n < 1 || n > 255) {
+      fprintf(stderr, "pair %zu: query length %zu outside [1,255]\n", pairs.size(), n);
+      return 1;
+    }
+    c.rb = rb, c.re = re, c.w = w;
+    c.idq = (int64_t)qer.size();
+    c.len2 = (int32_t)n;
+    for (size_t k = 0; k < n; ++k) qer.push_back((uint8_t)(line[k] - 48));
+    const unsigned long long d = re > rb ? (unsigned long long)(re - rb) : 0;
+    if (d <= GB_BSW_GLOBAL_MAX_TLEN) ccap += d + n, mcap += (size_t)GB_BSW_MD_CAP(d);  // longer ones: rejected or refused
+    pairs.push_back(c);
+  }
+  fclose(f);
+  FILE *info = out_file ? stdout : stderr;
+  fprintf(info, "Number of input pairs: %zu\n", pairs.size());
+  std::vector<uint32_t> cigar(ccap ? ccap : 1);
+  std::vector<char> md(mcap ? mcap : 1);
+  int64_t cused = 0, mused = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  st = gb_bsw_gen_cigar(&gp, ref, pairs.data(), (int64_t)pairs.size(), qer.data(), (int64_t)qer.size(), cigar.data(),
+                        (int64_t)cigar.size(), &cused, md.data(), (int64_t)md.size(), &mused);
+  const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (st) {
+    fprintf(stderr, "gb_bsw_gen_cigar failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  fprintf(info, "Executed MI355X CIGAR generation from the packed reference (gfx950)...\n");
+  fprintf(info, "Overall time = %0.3f s (%lld CIGAR operations, %lld MD bytes incl. host<->device copies)\n", sw_s,
+          (long long)cused, (long long)mused);
+  fprintf(info, "Total Pairs processed: %zu\n", pairs.size());
+  FILE *o = out_file ? fopen(out_file, "w") : stdout;
+  if (!o) {
+    fprintf(stderr, "Could not open file: %s\n", out_file);
+    return 1;
+  }
+  for (const auto &c : pairs) {
+    fprintf(o, "%d\t%d\t", c.score, c.nm);
+    if (c.n_cigar == 0) {
+      fputs("*\t*\n", o);
+      continue;
+    }
+    for (int32_t k = 0; k < c.n_cigar; ++k) {
+      const uint32_t op = cigar[(size_t)c.cigar_off + (size_t)k];
+      fprintf(o, "%u%c", op >> 4, "MID"[op & 3]);
+    }
+    fputc('\t', o);
+    fwrite(md.data() + c.md_off, 1, (size_t)c.md_len, o);
+    fputc('\n', o);
+  }
+  if (out_file) fclose(o);
+  gb_ref_destroy(ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
-  const char *pair_file = nullptr, *out_file = nullptr;
-  bool global = false, local = false;
+  const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr;
+  bool global = false, local = false, gencigar = false;
   for (int i = 1; i < argc; i += 2) {
-    if (!strcmp(argv[i], "-global") || !strcmp(argv[i], "-local")) {  // the two flags without a value
-      (argv[i][1] == 'g' ? global : local) = true;
+    if (!strcmp(argv[i], "-global") || !strcmp(argv[i], "-local") || !strcmp(argv[i], "-gencigar")) {
+      // the three flags without a value
+      (argv[i][2] == 'e' ? gencigar : argv[i][1] == 'g' ? global : local) = true;
       --i;
       continue;
     }
@@ -44,6 +137,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-gapo")) w_open = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-gape")) w_extend = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-pairs")) pair_file = argv[i + 1];
+    else if (!strcmp(argv[i], "-pac")) pac_file = argv[i + 1];
     else if (!strcmp(argv[i], "-t")) threads = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-b")) batch = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-o")) out_file = argv[i + 1];
@@ -57,6 +151,22 @@ int main(int argc, char **argv) {
   if (global && local) {
     fprintf(stderr, "bsw: -local and -global exclude each other\n");
     return 1;
+  }
+  if (gencigar) {
+    if (global || local) {
+      fprintf(stderr, "bsw: -gencigar excludes -global and -local\n");
+      return 1;
+    }
+    if (!pac_file) {
+      fprintf(stderr, "bsw: -gencigar needs -pac <file.pac>\n");
+      return 1;
+    }
+    gb_bsw_params gp;
+    gb_bsw_default_params(&gp);
+    gp.o_del = gp.o_ins = w_open;
+    gp.e_del = gp.e_ins = w_extend;
+    gb_bsw_fill_scmat(w_match, w_mismatch, w_ambig, gp.mat);
+    return run_gencigar(pac_file, pair_file, out_file, gp);
   }
   const size_t max_tlen = local ? GB_BSW_LOCAL_MAX_TLEN : 2047;
   FILE *f = fopen(pair_file, "r");

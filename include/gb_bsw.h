@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "gb.h"
+#include "gb_bsw_ref.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -127,6 +128,68 @@ int gb_bsw_global_band(const gb_bsw_params *params, int32_t len2, int32_t len1, 
 /* Device time of the calling thread's last gb_bsw_global on the current device, summed over its
  * chunks: the DP fill kernel and the traceback kernel (0 for a scores-only call). */
 int gb_bsw_global_timing(float *fill_ms, float *walk_ms);
+
+/* ---- CIGAR, NM and MD from reference coordinates: all of bwa_gen_cigar2 (tools/bwa/bwa.c:121-208)
+ * over a device-resident packed reference (gb_bsw_ref.h). Per pair the result is what
+ *   bwa_gen_cigar2(params->mat, o_del, e_del, o_ins, e_ins, w, l_pac, pac, len2, query, rb, re,
+ *                  &score, &n_cigar, &NM)
+ * yields, bit for bit: the region [rb, re) is fetched from the pac (bns_get_seq); for a reverse-strand
+ * region (rb >= l_pac) query and target are both reversed before the alignment, so that indels land
+ * leftmost on the forward strand (bwa.c:135-140), and the MD letters come from "TGCAN", which turns the
+ * complemented target bytes back into the forward strand's letters (bwa.c:172);
+ * len2 == re - rb with w == 0 takes the reference's shortcut, one len2 M operation scored as the plain
+ * sum of mat with no DP (bwa.c:141-149; a DP can score higher); every other pair gets the band of
+ * gb_bsw_global_band and ksw_global2. NM is as in gb_bsw_global. MD follows bwa.c:169-198. The
+ * caller's query bytes are never written.
+ *
+ * The reference's own rejections are per-pair results: rb >= re, a region bridging l_pac, and a region
+ * bns_get_seq's clamps shorten (rb < 0 or re > 2 l_pac) give n_cigar = 0, nm = -1, md_len = 0 and
+ * leave score as the caller set it (the reference does not write *score there).
+ *
+ * Refused for the whole call with GB_ERR_ARG before any device work, nothing written, the pair named
+ * in gb_last_error(): len2 outside [1, GB_BSW_MAX_QLEN]; w < 0; a query outside seq_buf_qer;
+ * re - rb > GB_BSW_GLOBAL_MAX_TLEN on a pair that is not rejected as above; gap penalties outside
+ * [0, 32768); e_del == 0 or e_ins == 0 (the band rule divides by them); md without cigar.
+ * params->zdrop, end_bonus and w are ignored. */
+typedef struct gb_bsw_cpair { /* 64 bytes */
+  int64_t rb, re;        /* region in the doubled coordinate space [0, 2 l_pac) */
+  int64_t idq;           /* query offset in seq_buf_qer */
+  int32_t len2, w;       /* query length; bwa_gen_cigar2's w_ argument */
+  int32_t score, n_cigar, nm, md_len; /* out */
+  int64_t cigar_off, md_off;          /* out */
+} gb_bsw_cpair;
+
+/* Pair p owns cigar[cigar_off .. cigar_off + n_cigar) and md[md_off .. md_off + md_len), both packed in
+ * pair order; md_len excludes the reference's terminating NUL and none is stored. *cigar_used and
+ * *md_used (may be NULL) receive the totals. The sum of (re - rb) + len2 over the pairs always suffices
+ * for cigar_cap and the sum of GB_BSW_MD_CAP(re - rb) for md_cap (every target base adds at most three
+ * characters, "0^A" for a one-base deletion between two insertions, and one final count follows). With
+ * either capacity below its total the call returns GB_ERR_ARG, sets both totals, fills the per-pair
+ * fields and leaves cigar[] and md[] untouched. cigar == NULL asks for scores only (mem_patch_reg's
+ * call, tools/bwa/bwamem.c:428): n_cigar = 0, nm = -1, md_len = 0, offsets 0; md must then be NULL.
+ * With cigar given and md == NULL, CIGAR and NM are produced without MD (md_len = 0, md_off = 0).
+ * num_pairs == 0 succeeds without a device. */
+#define GB_BSW_MD_CAP(len1) (3 * (int64_t)(len1) + 1)
+int gb_bsw_gen_cigar(const gb_bsw_params *params, const gb_ref *ref, gb_bsw_cpair *pairs, int64_t num_pairs,
+                     const uint8_t *seq_buf_qer, int64_t qer_bytes, uint32_t *cigar, int64_t cigar_cap,
+                     int64_t *cigar_used, char *md, int64_t md_cap, int64_t *md_used);
+
+/* mem_reg2aln's re-banding loop (tools/bwa/bwamem.c:1154-1163) around gb_bsw_gen_cigar: each pair
+ * starts from its own w capped at params->w << 2; it is final when its score equals that of its previous
+ * try, when w == params->w << 2, after three tries, or when score >= truesc[p] - params->mat[0];
+ * otherwise w doubles (capped again) and the pair is redone. A pair the reference rejects is final after
+ * one try. pairs[p].w receives the w of the pair's last try and tries[p] (may be NULL) their number. Each
+ * round is one gb_bsw_gen_cigar over the pairs still open. Needs 0 <= params->w < 2^28 in addition.
+ * infer_bw, the squeezing of leading and trailing deletions and the clipping (bwamem.c:1149-1153,
+ * 1166-1192) stay with the caller. */
+int gb_bsw_gen_cigar_retry(const gb_bsw_params *params, const gb_ref *ref, gb_bsw_cpair *pairs, int64_t num_pairs,
+                           const uint8_t *seq_buf_qer, int64_t qer_bytes, const int32_t *truesc, uint32_t *cigar,
+                           int64_t cigar_cap, int64_t *cigar_used, char *md, int64_t md_cap, int64_t *md_used,
+                           int32_t *tries);
+
+/* Device time of the calling thread's last gb_bsw_gen_cigar (or the rounds of a _retry) on the current
+ * device: the fetch kernel, the DP fill and traceback kernels summed over the chunks, the MD kernel. */
+int gb_bsw_gen_cigar_timing(float *fetch_ms, float *fill_ms, float *walk_ms, float *md_ms);
 
 /* ---- unbanded local alignment with sub-optimal score and start: bwa's ksw_align2 (tools/bwa/ksw.c:
  * 63-365), the call mem_matesw makes for mate rescue (tools/bwa/bwamem_pair.c:150-151). Per pair the
