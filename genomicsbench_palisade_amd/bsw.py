@@ -479,3 +479,91 @@ def gen_cigar_timing():
     t = [ctypes.c_float() for _ in range(4)]
     check(_decl_gencigar().gb_bsw_gen_cigar_timing(*[ctypes.byref(x) for x in t]), "gb_bsw_gen_cigar_timing")
     return tuple(x.value for x in t)
+
+
+# ---- seed extension from chains (mem_chain2aln, tools/bwa/bwamem.c:632-824) ----------
+
+# gb_bsw_seed (mem_seed_t), gb_bsw_region and gb_bsw_c2a_raw (include/gb_bsw.h)
+SEED_DTYPE = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])
+REGION_DTYPE = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("score", "<i4"),
+                         ("truesc", "<i4"), ("w", "<i4"), ("seedcov", "<i4"), ("seedlen0", "<i4"), ("chain", "<i4"),
+                         ("seed", "<i4"), ("_pad", "<i4")])
+C2A_RAW_DTYPE = np.dtype([("out6", "<i4", (2, 6)), ("tries", "<i4", (2,)), ("skipped", "<i4"), ("_pad", "<i4")])
+assert SEED_DTYPE.itemsize == 24 and REGION_DTYPE.itemsize == 56 and C2A_RAW_DTYPE.itemsize == 64
+REGION_FIELDS = ("rb", "re", "qb", "qe", "score", "truesc", "w", "seedcov", "seedlen0", "chain", "seed")
+
+
+def _decl_chain2aln():
+    L = _decl_gencigar()
+    if getattr(L, "_bsw_c2a_decl", False):
+        return L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.gb_bsw_chain2aln.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.gb_bsw_chain2aln_timing.argtypes = [vp, vp, vp, vp]
+    L._bsw_c2a_decl = True
+    return L
+
+
+def chain_csr(queries, chains):
+    """The three CSR levels of gb_bsw_chain2aln for a list of uint8 code arrays and, per read, a list of
+    chains, each a list of seeds (rbeg, qbeg, len, score): (qbuf, idq, l_query, read_chain_off,
+    chain_seed_off, seeds)."""
+    n = len(queries)
+    ql = np.array([len(q) for q in queries], np.int64)
+    idq = np.concatenate([[0], np.cumsum(ql)[:-1]]).astype(np.int64) if n else np.zeros(0, np.int64)
+    qbuf = np.concatenate([np.asarray(q, np.uint8) for q in queries]) if n else np.zeros(0, np.uint8)
+    rco = np.zeros(n + 1, np.int64)
+    rco[1:] = np.cumsum([len(c) for c in chains])
+    flat = [c for rc in chains for c in rc]
+    cso = np.zeros(len(flat) + 1, np.int64)
+    cso[1:] = np.cumsum([len(c) for c in flat])
+    seeds = np.zeros(int(cso[-1]), SEED_DTYPE)
+    rows = [s for c in flat for s in c]
+    if rows:
+        a = np.array(rows, np.int64).reshape(-1, 4)
+        seeds["rbeg"], seeds["qbeg"], seeds["len"], seeds["score"] = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
+    return np.ascontiguousarray(qbuf), idq, ql.astype(np.int32), rco, cso, seeds
+
+
+def chain2aln_csr(ref, qbuf, idq, l_query, read_chain_off, chain_seed_off, seeds, params=None, pen_clip5=5,
+                  pen_clip3=5, contig_end=None, want_raw=True, reg_cap=None):
+    """gb_bsw_chain2aln on CSR arrays (see chain_csr). Returns a dict: regs (REGION_DTYPE, packed in read
+    order), reg_off, n_reg (per read), raw (C2A_RAW_DTYPE per seed, or None). reg_cap defaults to the
+    number of seeds, which always suffices."""
+    params = params if params is not None else default_params()
+    qbuf = np.ascontiguousarray(qbuf, np.uint8)
+    idq = np.ascontiguousarray(idq, np.int64)
+    l_query = np.ascontiguousarray(l_query, np.int32)
+    rco = np.ascontiguousarray(read_chain_off, np.int64)
+    cso = np.ascontiguousarray(chain_seed_off, np.int64)
+    seeds = np.ascontiguousarray(seeds, SEED_DTYPE)
+    n = len(idq)
+    ce = None if contig_end is None else np.ascontiguousarray(contig_end, np.int64)
+    cap = len(seeds) if reg_cap is None else int(reg_cap)
+    regs = np.zeros(max(cap, 1), REGION_DTYPE)
+    reg_off, n_reg = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+    raw = np.zeros(max(len(seeds), 1), C2A_RAW_DTYPE) if want_raw else None
+    used = ctypes.c_int64(0)
+    check(_decl_chain2aln().gb_bsw_chain2aln(
+        ctypes.byref(params), int(pen_clip5), int(pen_clip3), ref.h, None if ce is None else ce.ctypes.data,
+        0 if ce is None else len(ce), _buf(qbuf), len(qbuf), n, _buf(idq), _buf(l_query), rco.ctypes.data,
+        cso.ctypes.data, _buf(seeds), regs.ctypes.data, cap, reg_off.ctypes.data, n_reg.ctypes.data,
+        ctypes.byref(used), raw.ctypes.data if want_raw else None), "gb_bsw_chain2aln")
+    return {"regs": regs[:used.value].copy(), "reg_off": reg_off[:n], "n_reg": n_reg[:n],
+            "raw": raw[:len(seeds)] if want_raw else None}
+
+
+def chain2aln(ref, queries, chains, **kw):
+    """mem_chain2aln for every read: queries is a list of uint8 code arrays, chains[r] the read's chains
+    in order, each a list of seeds (rbeg, qbeg, len, score). Keywords and result as chain2aln_csr."""
+    return chain2aln_csr(ref, *chain_csr(queries, chains), **kw)
+
+
+def chain2aln_timing():
+    """(gather_ms, ext_ms[4] = left w, left 2w, right w, right 2w, finish_ms, filter_ms): device time of this
+    thread's last chain2aln, summed over its chunks; 0 for a round that launched nothing."""
+    g, f, t = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+    e = (ctypes.c_float * 4)()
+    check(_decl_chain2aln().gb_bsw_chain2aln_timing(ctypes.byref(g), e, ctypes.byref(f), ctypes.byref(t)),
+          "gb_bsw_chain2aln_timing")
+    return g.value, tuple(e), f.value, t.value

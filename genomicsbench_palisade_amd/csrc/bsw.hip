@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/gb_bsw.h"
+#include "bsw_internal.h"
 #include "gb_common.h"
 
 static_assert(sizeof(gb_seqpair) == 72, "gb_seqpair must match SeqPair (bandedSWA.h:92-101)");
@@ -575,6 +576,8 @@ struct gb_bsw_batch {
   // grow-only: cached workspaces are refilled
   gb::DevBuf<gbbsw::Pair> d_pairs;
   gb::DevBuf<uint8_t> d_tgt, d_qry;
+  // what the kernels read: d_tgt / d_qry after an upload, the caller's device memory for gbbsw::run_resident
+  const uint8_t *tgt = nullptr, *qry = nullptr;
   gb::DevBuf<int32_t> d_out6, d_cells;
   gb::DevBuf<unsigned long long> d_total;  // [0] total cells, [1] work counter
   static constexpr int kTotals = 2;
@@ -648,41 +651,16 @@ int bsw_batch_new(gb_bsw_batch **out) {
   return GB_OK;
 }
 
-// Validate, classify and order the pairs (launch plan), then upload them and the sequence buffers
-// into B (buffers grow when too small).
-int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpair *pairs, int64_t n,
-                   const uint8_t *ref, int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes) {
-  GB_ARG(params && n >= 0 && (n == 0 || pairs), "gb_bsw_batch_create: bad arguments");
-  GB_ARG(n < (1ll << 32) - 1, "gb_bsw_batch_create: too many pairs");
-  GB_ARG(params->e_del > 0 && params->e_ins > 0, "gb_bsw_batch_create: gap extension must be > 0");
-  GB_ARG(ref_bytes >= 0 && qer_bytes >= 0 && (ref_bytes == 0 || ref) && (qer_bytes == 0 || qer),
-         "gb_bsw_batch_create: bad sequence buffers");
-  int st0 = GB_OK;
+// The launch plan: validate, classify and order the pairs, and upload their descriptors and the order
+// into B (buffers grow when too small). The pairs' offsets index sequence buffers of ref_bytes /
+// qer_bytes, which this does not touch. The caller has checked params and the buffer sizes.
+int bsw_batch_plan(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpair *pairs, int64_t n, int64_t ref_bytes,
+                   int64_t qer_bytes) {
   int mx = 0, mn = 0;
   for (int k = 0; k < 25; ++k) {
     mx = std::max(mx, (int)params->mat[k]);
     mn = std::min(mn, (int)params->mat[k]);
   }
-  // The sequence buffers (the bulk of the bytes) go up on a helper thread while this one builds
-  // the launch plan; the helper is joined on every return path.
-  if ((st0 = B->d_tgt.reserve((size_t)std::max<int64_t>(ref_bytes, 1)))) return st0;
-  if ((st0 = B->d_qry.reserve((size_t)std::max<int64_t>(qer_bytes, 1)))) return st0;
-  hipError_t up_err = hipSuccess;
-  struct Joiner {
-    std::thread t;
-    ~Joiner() {
-      if (t.joinable()) t.join();
-    }
-  } up;
-  auto upload = [&, dev = B->device, dt = B->d_tgt.get(), dq = B->d_qry.get()] {
-    up_err = hipSetDevice(dev);
-    if (up_err == hipSuccess && ref_bytes) up_err = hipMemcpy(dt, ref, (size_t)ref_bytes, hipMemcpyHostToDevice);
-    if (up_err == hipSuccess && qer_bytes) up_err = hipMemcpy(dq, qer, (size_t)qer_bytes, hipMemcpyHostToDevice);
-  };
-  if (ref_bytes + qer_bytes >= (16ll << 20))
-    up.t = std::thread(upload);
-  else
-    upload();  // small calls (the reference's 512-pair batches): no thread start-up
   // per pair: descriptor, kernel variant and sort key -- in parallel chunks for big batches; a bad
   // pair is reported by the sequential check below (first offending index)
   // variant: the pair-per-lane kernel needs qlen < 8*NCH (NCH <= 20) and scores that fit the 16-bit
@@ -835,6 +813,47 @@ int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpai
   if (n) GB_HIP(hipMemcpyAsync(B->d_order, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, B->stream));
   if (n) GB_HIP(hipMemcpyAsync(B->d_pairs, P.data(), (size_t)n * sizeof(gbbsw::Pair), hipMemcpyHostToDevice, B->stream));
   GB_HIP(hipStreamSynchronize(B->stream));  // the host vectors die on return
+  return GB_OK;
+}
+
+int bsw_check_args(const gb_bsw_params *params, const gb_seqpair *pairs, int64_t n, const uint8_t *ref,
+                   int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes) {
+  GB_ARG(params && n >= 0 && (n == 0 || pairs), "gb_bsw_batch_create: bad arguments");
+  GB_ARG(n < (1ll << 32) - 1, "gb_bsw_batch_create: too many pairs");
+  GB_ARG(params->e_del > 0 && params->e_ins > 0, "gb_bsw_batch_create: gap extension must be > 0");
+  GB_ARG(ref_bytes >= 0 && qer_bytes >= 0 && (ref_bytes == 0 || ref) && (qer_bytes == 0 || qer),
+         "gb_bsw_batch_create: bad sequence buffers");
+  return GB_OK;
+}
+
+// Upload the sequence buffers into B and plan the pairs on them.
+int bsw_batch_fill(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpair *pairs, int64_t n,
+                   const uint8_t *ref, int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes) {
+  int st0 = bsw_check_args(params, pairs, n, ref, ref_bytes, qer, qer_bytes);
+  if (st0) return st0;
+  // The sequence buffers (the bulk of the bytes) go up on a helper thread while this one builds
+  // the launch plan; the helper is joined on every return path.
+  if ((st0 = B->d_tgt.reserve((size_t)std::max<int64_t>(ref_bytes, 1)))) return st0;
+  if ((st0 = B->d_qry.reserve((size_t)std::max<int64_t>(qer_bytes, 1)))) return st0;
+  B->tgt = B->d_tgt;
+  B->qry = B->d_qry;
+  hipError_t up_err = hipSuccess;
+  struct Joiner {
+    std::thread t;
+    ~Joiner() {
+      if (t.joinable()) t.join();
+    }
+  } up;
+  auto upload = [&, dev = B->device, dt = B->d_tgt.get(), dq = B->d_qry.get()] {
+    up_err = hipSetDevice(dev);
+    if (up_err == hipSuccess && ref_bytes) up_err = hipMemcpy(dt, ref, (size_t)ref_bytes, hipMemcpyHostToDevice);
+    if (up_err == hipSuccess && qer_bytes) up_err = hipMemcpy(dq, qer, (size_t)qer_bytes, hipMemcpyHostToDevice);
+  };
+  if (ref_bytes + qer_bytes >= (16ll << 20))
+    up.t = std::thread(upload);
+  else
+    upload();  // small calls (the reference's 512-pair batches): no thread start-up
+  if ((st0 = bsw_batch_plan(B, params, pairs, n, ref_bytes, qer_bytes))) return st0;
   if (up.t.joinable()) up.t.join();
   GB_HIP(up_err);
   return GB_OK;
@@ -871,8 +890,8 @@ int gb_bsw_batch_run(gb_bsw_batch *B) {
     gbbsw::LaneArgs L;
     L.pairs = B->d_pairs;
     L.order = B->d_order;
-    L.tgt = B->d_tgt;
-    L.qry = B->d_qry;
+    L.tgt = B->tgt;
+    L.qry = B->qry;
     L.out6 = B->d_out6;
     L.cells = B->d_cells;
     L.total_cells = B->d_total;
@@ -922,8 +941,8 @@ int gb_bsw_batch_run(gb_bsw_batch *B) {
       A.pairs = B->d_pairs;
       A.list = B->d_order + B->seg[5];
       A.n = nw;
-      A.tgt = B->d_tgt;
-      A.qry = B->d_qry;
+      A.tgt = B->tgt;
+      A.qry = B->qry;
       A.out6 = B->d_out6;
       A.cells = B->d_cells;
       A.total_cells = B->d_total;
@@ -1252,7 +1271,48 @@ int small_call(const gb_bsw_params *params, gb_seqpair *pairs, int64_t n, const 
   return me.status;
 }
 
+// The calling thread's cached batch on the current device. Never freed (freeing at thread exit could
+// run after the HIP runtime is torn down).
+int cached_batch(gb_bsw_batch **out) {
+  thread_local std::vector<std::pair<int, gb_bsw_batch *>> ws;
+  int dev = 0;
+  GB_HIP(hipGetDevice(&dev));
+  for (auto &w : ws)
+    if (w.first == dev) {
+      *out = w.second;
+      return GB_OK;
+    }
+  gb_bsw_batch *B = nullptr;
+  if (int st = bsw_batch_new(&B)) return st;
+  ws.emplace_back(dev, B);
+  *out = B;
+  return GB_OK;
+}
+
 }  // namespace
+
+namespace gbbsw {
+
+int run_resident(const gb_bsw_params *params, const gb_seqpair *pairs, int64_t n, const uint8_t *d_tgt,
+                 int64_t tgt_bytes, const uint8_t *d_qry, int64_t qry_bytes, int32_t *out6, const int32_t **d_out6,
+                 float *kernel_ms) {
+  int st = bsw_check_args(params, pairs, n, d_tgt, tgt_bytes, d_qry, qry_bytes);
+  if (st) return st;
+  gb_bsw_batch *B = nullptr;
+  if ((st = cached_batch(&B))) return st;
+  if ((st = bsw_batch_plan(B, params, pairs, n, tgt_bytes, qry_bytes))) return st;
+  B->tgt = d_tgt;
+  B->qry = d_qry;
+  if ((st = gb_bsw_batch_run(B))) return st;
+  if ((st = gb_bsw_batch_results(B, nullptr, out6, nullptr, nullptr))) return st;
+  float ms = 0.f;
+  if ((st = gb_bsw_batch_timing(B, &ms))) return st;
+  if (kernel_ms) *kernel_ms += ms;
+  if (d_out6) *d_out6 = B->d_out6;
+  return GB_OK;
+}
+
+}  // namespace gbbsw
 
 extern "C" {
 
@@ -1267,17 +1327,9 @@ int gb_bsw_get_scores16_ex(const gb_bsw_params *params, gb_seqpair *pairs, int64
   // one cached batch per (host thread, device): the reference calls getScores16 once per batch of
   // 512 pairs (main_banded.cpp:896-909), so streams, events and buffers are reused across calls.
   // Never freed (freeing at thread exit could run after the HIP runtime is torn down).
-  thread_local std::vector<std::pair<int, gb_bsw_batch *>> ws;
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
   gb_bsw_batch *B = nullptr;
-  for (auto &w : ws)
-    if (w.first == dev) B = w.second;
-  int st = GB_OK;
-  if (!B) {
-    if ((st = bsw_batch_new(&B))) return st;
-    ws.emplace_back(dev, B);
-  }
+  int st = cached_batch(&B);
+  if (st) return st;
   if ((st = bsw_batch_fill(B, params, pairs, n, ref, ref_bytes, qer, qer_bytes))) return st;
   st = gb_bsw_batch_run(B);
   if (!st) st = gb_bsw_batch_results(B, pairs, nullptr, nullptr, total_cells);

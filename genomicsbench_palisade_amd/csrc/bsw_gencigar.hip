@@ -32,19 +32,10 @@
 
 #include "../../include/gb_bsw.h"
 #include "bsw_global_internal.h"
+#include "bsw_ref_internal.h"
 #include "gb_common.h"
 
 static_assert(sizeof(gb_bsw_cpair) == 64, "gb_bsw_cpair is 64 bytes (include/gb_bsw.h)");
-
-// The packed reference. The host copy lives until the first device use (ensure_device).
-struct gb_ref {
-  int64_t l_pac = 0;
-  std::mutex mu;
-  std::vector<uint8_t> host;
-  int device = -1;
-  int64_t n_words = 0;  // 32-bit words on the device: the pac, zero-padded, plus two words of slack
-  gb::DevBuf<uint32_t> d_pac;
-};
 
 namespace gbgc {
 
@@ -73,16 +64,6 @@ struct FetchArgs {
   int8_t mat[28];
 };
 
-// 16 bases starting at pac index b0 (which may lie outside [0, l_pac) in a slice's padding: the
-// word indices are clamped, the bases there mean nothing), first base in bits 31-30
-__device__ __forceinline__ uint32_t bases16(const uint32_t *pac, int64_t n_words, int64_t b0) {
-  const int64_t wi = b0 >> 4;
-  const int64_t i0 = min(max(wi, (int64_t)0), n_words - 1), i1 = min(max(wi + 1, (int64_t)0), n_words - 1);
-  // base l sits in byte l >> 2 at shift (~l & 3) << 1: most significant first once the bytes are swapped
-  const uint64_t v = (uint64_t)__builtin_bswap32(pac[i0]) << 32 | __builtin_bswap32(pac[i1]);
-  return (uint32_t)((v << (2 * (int)(b0 & 15))) >> 32);
-}
-
 __global__ __launch_bounds__(64 * kFetchWaves) void bsw_gencigar_fetch_kernel(FetchArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * kFetchWaves + (threadIdx.x >> 6);
@@ -90,38 +71,10 @@ __global__ __launch_bounds__(64 * kFetchWaves) void bsw_gencigar_fetch_kernel(Fe
   const FetchItem it = A.items[p];
   const uint32_t cx = (it.flags & kComplement) ? 0xFFFFFFFFu : 0u;  // 3 - x == ~x on two bits
   const bool back = (it.flags & kBackward) != 0;
-  const int64_t nch = ((int64_t)it.len + 15) >> 4;
-  for (int64_t c = lane; c < nch; c += 64) {
-    // forward: out[16c + j] = base src + 16c + j; backward: out[16c + j] = base src - 16c - j
-    const int64_t b0 = back ? it.src - 16 * c - 15 : it.src + 16 * c;
-    const uint32_t v = bases16(A.pac, A.n_words, b0) ^ cx;
-    uint32_t o[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int j = 4 * d + k;
-        const int sh = back ? 2 * j : 30 - 2 * j;
-        w |= ((v >> sh) & 3u) << (8 * k);
-      }
-      o[d] = w;
-    }
-    *reinterpret_cast<uint4 *>(A.tgt + it.t_dst + 16 * c) = make_uint4(o[0], o[1], o[2], o[3]);
-  }
+  fetch_bases(A.pac, A.n_words, it.src, it.len, back, cx, A.tgt + it.t_dst, lane);
   const bool rev = it.q_dst >= 0;
-  if (rev) {  // the reversed query, four bytes per store; the slice is padded to a multiple of 4
-    const uint8_t *q = A.qry + it.q_src;
-    for (int g = lane; 4 * g < it.qlen; g += 64) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int i = 4 * g + b;
-        if (i < it.qlen) w |= (uint32_t)q[it.qlen - 1 - i] << (8 * b);
-      }
-      *reinterpret_cast<uint32_t *>(A.qry + it.q_dst + 4 * g) = w;
-    }
-  }
+  // the reversed query; the slice is padded to a multiple of 4
+  if (rev) reverse_query(A.qry + it.q_src, it.qlen, A.qry + it.q_dst, lane);
   if (it.flags & kShortcut) {  // bwa.c:148-149 (len == qlen); the sum does not depend on the order
     const uint8_t *q = A.qry + it.q_src;
     int s = 0;

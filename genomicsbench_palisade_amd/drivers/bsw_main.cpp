@@ -24,6 +24,14 @@
 // query. One line per pair, score NM CIGAR MD (tab separated), goes to the -o file or to stdout as for
 // -global; a pair the reference rejects prints * for CIGAR and MD. -gencigar excludes -global and
 // -local.
+// -chain2aln -pac <file.pac> <file> (or -pairs <file>) runs the step before it: all of bwa's
+// mem_chain2aln (gb_bsw_chain2aln), from chains of seeds to alignment regions. Per read one line, the
+// bases ('0'..'4') and the number of chains, then one line per chain with four numbers per seed, "rbeg
+// qbeg len score", in bwa's doubled coordinate space. -w, -zdrop, -clip5 and -clip3 set opt->w, zdrop
+// and pen_clip5 / pen_clip3 (100, 100, 5, 5); -contigs e1,e2,... gives the contigs' cumulative ends, the
+// last equal to l_pac (one contig without it). One line per region, read rb re qb qe score truesc w
+// seedcov seedlen0 (tab separated; read = index of the read), goes to the -o file or to stdout as for
+// -global. -chain2aln excludes the other modes.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -119,11 +127,128 @@ static int run_gencigar(const char *pac_file, const char *pair_file, const char 
   return 0;
 }
 
+// -chain2aln: per read "bases n_chains", then per chain "rbeg qbeg len score" per seed
+static int run_chain2aln(const char *pac_file, const char *in_file, const char *out_file, const gb_bsw_params &gp,
+                         int clip5, int clip3, const char *contigs) {
+  gb_ref *ref = nullptr;
+  int st = gb_ref_load_pac(pac_file, &ref);
+  if (st) {
+    fprintf(stderr, "gb_ref_load_pac failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  std::vector<int64_t> contig_end;
+  for (const char *c = contigs; c && *c;) {
+    char *e = nullptr;
+    contig_end.push_back(strtoll(c, &e, 10));
+    if (e == c) {
+      fprintf(stderr, "bsw: -contigs expects e1,e2,...\n");
+      return 1;
+    }
+    c = *e == ',' ? e + 1 : e;
+  }
+  FILE *f = fopen(in_file, "r");
+  if (!f) {
+    fprintf(stderr, "Could not open file: %s\n", in_file);
+    return 1;
+  }
+  std::vector<uint8_t> qer;
+  std::vector<int64_t> idq, rco(1, 0), cso(1, 0);
+  std::vector<int32_t> lq;
+  std::vector<gb_bsw_seed> seeds;
+  std::vector<char> line(1 << 20);
+  while (fgets(line.data(), (int)line.size(), f)) {
+    char *p = line.data();
+    size_t n = 0;
+    while (p[n] >= '0' && p[n] <= '4') ++n;
+    const long nc = strtol(p + n, nullptr, 10);
+    if (n == 0 && (p[0] == '\n' || p[0] == '\r')) continue;
+    if (n == 0 || nc < 0) {
+      fprintf(stderr, "read %zu: expected \"bases n_chains\"\n", lq.size());
+      return 1;
+    }
+    idq.push_back((int64_t)qer.size());
+    lq.push_back((int32_t)n);
+    for (size_t k = 0; k < n; ++k) qer.push_back((uint8_t)(p[k] - 48));
+    for (long c = 0; c < nc; ++c) {
+      if (!fgets(line.data(), (int)line.size(), f)) {
+        fprintf(stderr, "read %zu: %ld chain lines are missing\n", lq.size() - 1, nc - c);
+        return 1;
+      }
+      char *q = line.data(), *e = nullptr;
+      for (;;) {
+        long long v[4];
+        int k = 0;
+        for (; k < 4; ++k) {
+          v[k] = strtoll(q, &e, 10);
+          if (e == q) break;
+          q = e;
+        }
+        if (k == 0) break;
+        if (k < 4) {
+          fprintf(stderr, "read %zu chain %ld: a seed is four numbers, rbeg qbeg len score\n", lq.size() - 1, c);
+          return 1;
+        }
+        gb_bsw_seed s;
+        memset(&s, 0, sizeof(s));
+        s.rbeg = v[0], s.qbeg = (int32_t)v[1], s.len = (int32_t)v[2], s.score = (int32_t)v[3];
+        seeds.push_back(s);
+      }
+      cso.push_back((int64_t)seeds.size());
+    }
+    rco.push_back((int64_t)cso.size() - 1);
+  }
+  fclose(f);
+  FILE *info = out_file ? stdout : stderr;
+  fprintf(info, "Number of input reads: %zu (%zu chains, %zu seeds)\n", lq.size(), cso.size() - 1, seeds.size());
+  std::vector<gb_bsw_region> regs(seeds.size() ? seeds.size() : 1);
+  std::vector<int64_t> reg_off(lq.size() ? lq.size() : 1);
+  std::vector<int32_t> n_reg(lq.size() ? lq.size() : 1);
+  int64_t used = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  st = gb_bsw_chain2aln(&gp, clip5, clip3, ref, contig_end.empty() ? nullptr : contig_end.data(),
+                        (int64_t)contig_end.size(), qer.data(), (int64_t)qer.size(), (int64_t)lq.size(), idq.data(),
+                        lq.data(), rco.data(), cso.data(), seeds.data(), regs.data(), (int64_t)seeds.size(),
+                        reg_off.data(), n_reg.data(), &used, nullptr);
+  const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (st) {
+    fprintf(stderr, "gb_bsw_chain2aln failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  fprintf(info, "Executed MI355X seed extension from chains on the packed reference (gfx950)...\n");
+  fprintf(info, "Overall time = %0.3f s (%lld regions incl. host<->device copies)\n", sw_s, (long long)used);
+  fprintf(info, "Total reads processed: %zu\n", lq.size());
+  FILE *o = out_file ? fopen(out_file, "w") : stdout;
+  if (!o) {
+    fprintf(stderr, "Could not open file: %s\n", out_file);
+    return 1;
+  }
+  for (size_t r = 0; r < lq.size(); ++r)
+    for (int32_t k = 0; k < n_reg[r]; ++k) {
+      const gb_bsw_region &a = regs[(size_t)reg_off[r] + (size_t)k];
+      fprintf(o, "%zu\t%lld\t%lld\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", r, (long long)a.rb, (long long)a.re, a.qb, a.qe,
+              a.score, a.truesc, a.w, a.seedcov, a.seedlen0);
+    }
+  if (out_file) fclose(o);
+  gb_ref_destroy(ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
-  const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr;
-  bool global = false, local = false, gencigar = false;
+  const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr, *contigs = nullptr;
+  bool global = false, local = false, gencigar = false, chain2aln = false;
+  int band = 100, zdrop_arg = 100, clip5 = 5, clip3 = 5;
   for (int i = 1; i < argc; i += 2) {
+    if (!strcmp(argv[i], "-chain2aln")) {
+      chain2aln = true;
+      --i;
+      continue;
+    }
+    if (argv[i][0] != '-') {  // -chain2aln's input file may stand alone
+      pair_file = argv[i];
+      --i;
+      continue;
+    }
     if (!strcmp(argv[i], "-global") || !strcmp(argv[i], "-local") || !strcmp(argv[i], "-gencigar")) {
       // the three flags without a value
       (argv[i][2] == 'e' ? gencigar : argv[i][1] == 'g' ? global : local) = true;
@@ -138,6 +263,11 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-gape")) w_extend = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-pairs")) pair_file = argv[i + 1];
     else if (!strcmp(argv[i], "-pac")) pac_file = argv[i + 1];
+    else if (!strcmp(argv[i], "-contigs")) contigs = argv[i + 1];
+    else if (!strcmp(argv[i], "-w")) band = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-zdrop")) zdrop_arg = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-clip5")) clip5 = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-clip3")) clip3 = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-t")) threads = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-b")) batch = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-o")) out_file = argv[i + 1];
@@ -151,6 +281,24 @@ int main(int argc, char **argv) {
   if (global && local) {
     fprintf(stderr, "bsw: -local and -global exclude each other\n");
     return 1;
+  }
+  if (chain2aln) {
+    if (global || local || gencigar) {
+      fprintf(stderr, "bsw: -chain2aln excludes -global, -local and -gencigar\n");
+      return 1;
+    }
+    if (!pac_file) {
+      fprintf(stderr, "bsw: -chain2aln needs -pac <file.pac>\n");
+      return 1;
+    }
+    gb_bsw_params gp;
+    gb_bsw_default_params(&gp);
+    gp.o_del = gp.o_ins = w_open;
+    gp.e_del = gp.e_ins = w_extend;
+    gp.w = band;
+    gp.zdrop = zdrop_arg;
+    gb_bsw_fill_scmat(w_match, w_mismatch, w_ambig, gp.mat);
+    return run_chain2aln(pac_file, pair_file, out_file, gp, clip5, clip3, contigs);
   }
   if (gencigar) {
     if (global || local) {

@@ -238,6 +238,79 @@ int gb_bsw_local_xtra(const gb_bsw_params *params, int32_t len2, int32_t min_see
 /* Device time of the calling thread's last gb_bsw_local on the current device, summed over its chunks. */
 int gb_bsw_local_timing(float *kernel_ms);
 
+/* ---- seed extension from chains: all of bwa's mem_chain2aln (tools/bwa/bwamem.c:632-824) over a
+ * device-resident packed reference. In go the seeds an SA lookup produces, grouped into chains and the
+ * chains into reads; out come the alignment regions mem_chain2aln would push, bit for bit, in its order:
+ * the chains of a read in the order given into one region list (mem_align1_core passes the same regs for
+ * every chain of a read), the seeds of a chain by decreasing score << 32 | index. rb, re, qb, qe, truesc
+ * and w are what gb_bsw_gen_cigar_retry consumes. rid, frac_rep and everything after mem_chain2aln
+ * (mem_sort_dedup_patch and on) stay with the caller.
+ *
+ * params gives mat, the gap penalties, zdrop and w = opt->w; params->end_bonus is ignored: left
+ * extensions pass pen_clip5 as ksw_extend2's end_bonus, right extensions pen_clip3. contig_end (may be
+ * NULL: one contig) holds the n_contigs cumulative end offsets of the contigs on the forward strand, the
+ * last equal to l_pac: all of .ann that bns_fetch_seq (bntseq.c:427-446) needs to clip a chain's window
+ * to the contig, or its reverse-strand mirror, that holds seeds[0].rbeg.
+ *
+ * Three CSR levels: read r has the query seq_buf_qer[idq[r] .. idq[r] + l_query[r]) (codes 0..4) and the
+ * chains read_chain_off[r] .. read_chain_off[r + 1); chain c the seeds chain_seed_off[c] ..
+ * chain_seed_off[c + 1). read_chain_off[0] == 0 and chain_seed_off[0] == 0; the number of chains is
+ * read_chain_off[n_reads], the number of seeds chain_seed_off[that].
+ *
+ * Every seed is extended (a seed's extension depends on the seed, the read and its chain's window
+ * only); the containment test against the read's earlier regions (bwamem.c:671-703) is applied
+ * afterwards over the finished results, so the regions are the reference's.
+ *
+ * Refused for the whole call with GB_ERR_ARG before any device work, nothing written, the read, chain or
+ * seed named in gb_last_error(): l_query < 1; an extension's query part (qbeg, or l_query - qbeg - len)
+ * above GB_BSW_MAX_QLEN; len < 1, score < 1, qbeg < 0, qbeg + len > l_query; rbeg < 0 or
+ * rbeg + len > 2 l_pac; a seed bridging l_pac; seeds of one chain on both strands; a seed that does not
+ * lie inside its chain's window after the clip to the contig of seeds[0] (bwa never builds such a chain);
+ * a window of 2^31 bases or more; gap penalties outside [0, 32768); e_del == 0 or e_ins == 0; w outside
+ * [0, 2^28); an empty chain (the reference returns on c->n == 0; refused so that indices stay aligned);
+ * offsets that decrease; a query outside seq_buf_qer; contig_end not increasing or not ending at l_pac;
+ * 2^31 seeds or more. n_reads == 0 succeeds without a device. */
+typedef struct gb_bsw_seed { /* mem_seed_t (bwamem.h), 24 bytes */
+  int64_t rbeg;
+  int32_t qbeg, len, score;
+  int32_t pad;
+} gb_bsw_seed;
+
+typedef struct gb_bsw_region { /* 56 bytes */
+  int64_t rb, re;
+  int32_t qb, qe, score, truesc, w, seedcov, seedlen0;
+  int32_t chain, seed; /* the chain's and the seed's index in the call */
+  int32_t pad;
+} gb_bsw_region;
+
+/* What every extension returned, kept or not. Side 0 is the left extension, side 1 the right one.
+ * out6[side] = {score, qle, tle, gtle, gscore, max_off} of that side's last try; tries[side] is 0 when the
+ * side had nothing to extend (out6 is then all zero), else 1 or 2; skipped = 1 when the containment test
+ * dropped the seed. */
+typedef struct gb_bsw_c2a_raw { /* 64 bytes */
+  int32_t out6[2][6];
+  int32_t tries[2];
+  int32_t skipped, pad;
+} gb_bsw_c2a_raw;
+
+/* Read r owns regs[reg_off[r] .. reg_off[r] + n_reg[r]), packed in read order; *reg_used (may be NULL)
+ * receives the total. The number of seeds always suffices for reg_cap. With reg_cap below the total the
+ * call returns GB_ERR_ARG, sets *reg_used to the count required, fills reg_off and n_reg and leaves
+ * regs[] untouched. raw (may be NULL) has one record per seed. The reads are cut into chunks when the
+ * gathered bytes (twice the windows plus twice the queries) pass 256 MiB (GB_BSW_C2A_BYTES overrides).
+ * Buffers are cached per (calling thread, device). */
+int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen_clip3, const gb_ref *ref,
+                     const int64_t *contig_end, int64_t n_contigs, const uint8_t *seq_buf_qer, int64_t qer_bytes,
+                     int64_t n_reads, const int64_t *idq, const int32_t *l_query, const int64_t *read_chain_off,
+                     const int64_t *chain_seed_off, const gb_bsw_seed *seeds, gb_bsw_region *regs, int64_t reg_cap,
+                     int64_t *reg_off, int32_t *n_reg, int64_t *reg_used, gb_bsw_c2a_raw *raw);
+
+/* Device time of the calling thread's last gb_bsw_chain2aln on the current device, summed over its
+ * chunks: the gather kernel; the extension launches of the four rounds, ext_ms[0] left at w, [1] left at
+ * 2 w, [2] right at w, [3] right at 2 w (0 for a round that had no seed and launched nothing); the finish
+ * kernel; the filter, scan and emit kernels. */
+int gb_bsw_chain2aln_timing(float *gather_ms, float ext_ms[4], float *finish_ms, float *filter_ms);
+
 #ifdef __cplusplus
 }
 #endif
