@@ -17,7 +17,7 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle
+.PHONY: all ref clean oracle mkchain-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -82,6 +82,17 @@ tests/_build/liblds_poison.so: tests/cpp/lds_poison.hip
 tests/_build/devbuf_check: tests/cpp/devbuf_check.cpp $(LIB)/libgb.so $(HDRS)
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall -o $@ $< -L$(LIB) -lgb -Wl,-rpath,'$$ORIGIN/../../$(LIB)'
+
+# the host path of gb_bsw_seeds2chains under the address and undefined-behaviour sanitizers: a stand-alone
+# program (its own main, no device touched) built from the library's two source files it needs, and run.
+# Not part of `all`.
+mkchain-sanitize: tests/_build/mkchain_host_check
+	tests/_build/mkchain_host_check
+tests/_build/mkchain_host_check: tests/cpp/mkchain_host_check.cpp $(CSRC)/bsw_mkchain.hip $(CSRC)/gb_common.cpp $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_mkchain.hip \
+	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:
 	$(MAKE) -s -C oracle all

@@ -567,3 +567,109 @@ def chain2aln_timing():
     check(_decl_chain2aln().gb_bsw_chain2aln_timing(ctypes.byref(g), e, ctypes.byref(f), ctypes.byref(t)),
           "gb_bsw_chain2aln_timing")
     return g.value, tuple(e), f.value, t.value
+
+
+# ---- chains from seeds (mem_chain after mem_collect_intv, mem_chain_flt; tools/bwa/bwamem.c:251-385) ----
+
+# gb_bsw_mem and gb_bsw_chain_info (include/gb_bsw.h)
+MEM_DTYPE = np.dtype([("read", "<i4"), ("m", "<i4"), ("n", "<i4"), ("n_coord", "<i4"), ("s", "<i8")])
+CHAIN_INFO_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("is_alt", "<i4"), ("w", "<i4"), ("kept", "<i4"),
+                             ("l_rep", "<i4"), ("frac_rep", "<f4")])
+assert MEM_DTYPE.itemsize == 24 and CHAIN_INFO_DTYPE.itemsize == 32
+CHAIN_INFO_FIELDS = ("pos", "rid", "is_alt", "w", "kept", "l_rep", "frac_rep")
+MKCHAIN_DEV_COORDS = 65536  # GB_BSW_MKCHAIN_DEV_COORDS
+
+
+class ChainOpt(ctypes.Structure):
+    """gb_bsw_chain_opt: the mem_opt_t fields mem_chain and mem_chain_flt read."""
+    _fields_ = [("w", ctypes.c_int32), ("max_chain_gap", ctypes.c_int32), ("max_occ", ctypes.c_int32),
+                ("min_seed_len", ctypes.c_int32), ("min_chain_weight", ctypes.c_int32),
+                ("max_chain_extend", ctypes.c_int32), ("mask_level", ctypes.c_float), ("drop_ratio", ctypes.c_float)]
+
+
+def _decl_mkchain():
+    L = _decl_chain2aln()
+    if getattr(L, "_bsw_mkchain_decl", False):
+        return L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.gb_bsw_chain_default_opt.argtypes = [vp]
+    L.gb_bsw_chain_default_opt.restype = None
+    L.gb_bsw_seeds2chains.argtypes = [vp, i32, i64, vp, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64,
+                                      vp, vp]
+    L.gb_bsw_seeds2chains_timing.argtypes = [vp, vp, vp, vp]
+    L._bsw_mkchain_decl = True
+    return L
+
+
+def chain_opt(**kw):
+    """bwa's defaults (bwamem.c:50-86): w 100, max_chain_gap 10000, max_occ 500, min_seed_len 19,
+    min_chain_weight 0, max_chain_extend 1 << 30, mask_level 0.5, drop_ratio 0.5; keywords override."""
+    o = ChainOpt()
+    _decl_mkchain().gb_bsw_chain_default_opt(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, float(v) if k in ("mask_level", "drop_ratio") else int(v))
+    return o
+
+
+def mems_from_smems(smems, counts):
+    """gb_bsw_mem records from gb_fmi_results' structured array (fields rid, m, n, s) and the counts of
+    gb_fmi_sa_entries."""
+    mems = np.zeros(len(smems), MEM_DTYPE)
+    mems["read"], mems["m"], mems["n"], mems["s"] = smems["rid"], smems["m"], smems["n"], smems["s"]
+    mems["n_coord"] = counts
+    return mems
+
+
+def seeds2chains_raw(l_pac, l_query, mems, coords, opt=None, stage=1, contig_end=None, contig_is_alt=None,
+                     chain_cap=None, seed_cap=None, fill=0, n_coords=None):
+    """gb_bsw_seeds2chains without the status check: a dict with status, chains_used, seeds_used and the
+    four output arrays at their full capacity, every byte preset to `fill` (what a refused call or a call
+    with too small a cap must leave alone). n_coords overrides the coordinate count passed (the caps keep
+    following len(coords)): for the refusals that look at the count alone."""
+    opt = opt if opt is not None else chain_opt()
+    l_query = np.ascontiguousarray(l_query, np.int32)
+    mems = np.ascontiguousarray(mems, MEM_DTYPE)
+    coords = np.ascontiguousarray(coords, np.int64)
+    n = len(l_query)
+    ce = None if contig_end is None else np.ascontiguousarray(contig_end, np.int64)
+    alt = None if contig_is_alt is None else np.ascontiguousarray(contig_is_alt, np.uint8)
+    ccap = len(coords) if chain_cap is None else int(chain_cap)
+    scap = len(coords) if seed_cap is None else int(seed_cap)
+
+    def out(count, dtype):
+        a = np.zeros(count, dtype)
+        a.view(np.uint8)[:] = fill
+        return a
+    rco, cso = out(n + 1, np.int64), out(ccap + 1, np.int64)
+    seeds, info = out(max(scap, 1), SEED_DTYPE), out(max(ccap, 1), CHAIN_INFO_DTYPE)
+    cu, su = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    st = _decl_mkchain().gb_bsw_seeds2chains(
+        ctypes.byref(opt), int(stage), int(l_pac), None if ce is None else ce.ctypes.data,
+        None if alt is None else alt.ctypes.data, 0 if ce is None else len(ce), n, _buf(l_query), _buf(mems),
+        len(mems), _buf(coords), len(coords) if n_coords is None else int(n_coords), rco.ctypes.data, cso.ctypes.data, seeds.ctypes.data, info.ctypes.data,
+        ccap, scap, ctypes.byref(cu), ctypes.byref(su))
+    return {"status": st, "chains_used": cu.value, "seeds_used": su.value, "read_chain_off": rco,
+            "chain_seed_off": cso, "seeds": seeds, "info": info}
+
+
+def seeds2chains(l_pac, l_query, mems, coords, **kw):
+    """gb_bsw_seeds2chains: mem_chain (stage=0) and mem_chain_flt (stage=1, the default) for every read.
+    mems is a MEM_DTYPE array grouped by read (mems_from_smems), coords the coordinates in SMEM order.
+    Keywords: opt (chain_opt()), stage, contig_end, contig_is_alt, chain_cap, seed_cap (the caps default to
+    the number of coordinates, which always suffices). Returns a dict with the CSR arguments of
+    chain2aln_csr (read_chain_off, chain_seed_off, seeds) and info (CHAIN_INFO_DTYPE per chain)."""
+    r = seeds2chains_raw(l_pac, l_query, mems, coords, **kw)
+    check(r["status"], "gb_bsw_seeds2chains")
+    nc, ns = r["chains_used"], r["seeds_used"]
+    return {"read_chain_off": r["read_chain_off"], "chain_seed_off": r["chain_seed_off"][:nc + 1],
+            "seeds": r["seeds"][:ns], "info": r["info"][:nc]}
+
+
+def seeds2chains_timing():
+    """(build_ms, filter_ms, emit_ms, host_reads) of this thread's last seeds2chains: the device time of the
+    three kernel groups (0 on the host path) and the reads that took the host path."""
+    t = [ctypes.c_float() for _ in range(3)]
+    h = ctypes.c_int64(0)
+    check(_decl_mkchain().gb_bsw_seeds2chains_timing(*[ctypes.byref(x) for x in t], ctypes.byref(h)),
+          "gb_bsw_seeds2chains_timing")
+    return t[0].value, t[1].value, t[2].value, h.value

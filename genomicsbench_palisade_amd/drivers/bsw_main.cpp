@@ -32,6 +32,16 @@
 // last equal to l_pac (one contig without it). One line per region, read rb re qb qe score truesc w
 // seedcov seedlen0 (tab separated; read = index of the read), goes to the -o file or to stdout as for
 // -global. -chain2aln excludes the other modes.
+// -mkchains <file> (or -pairs <file>) runs the step before that one: bwa's mem_chain and mem_chain_flt
+// (gb_bsw_seeds2chains), from the SMEMs of a read and their reference coordinates to chains. Per read one
+// line, "l_query n_smems", then one line per SMEM, "m n s c1 c2 ...": the seed is query [m, n] inclusive,
+// s the size of its interval and c1 ... the coordinates an SA lookup gives for it (gb_fmi_sa_entries), in
+// bwa's doubled coordinate space. -lpac gives l_pac (or -contigs e1,e2,..., whose last entry is l_pac),
+// -alt a1,a2,... one 0 / 1 per contig, -stage 0 stops after mem_chain (1, the default, adds
+// mem_chain_flt); -w, -maxgap, -maxocc, -minseed, -minweight, -maxextend, -mask and -drop set the options
+// (100, 10000, 500, 19, 0, 2^30, 0.5, 0.5). One line per chain goes to the -o file or to stdout as for
+// -global: read pos rid is_alt weight kept n_seeds (tab separated), then per seed, in mem_print_chain's
+// field order, score;len;qbeg,rbeg. -mkchains excludes the other modes and needs no -pac.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -233,18 +243,176 @@ static int run_chain2aln(const char *pac_file, const char *in_file, const char *
   return 0;
 }
 
+struct MkOpt {
+  gb_bsw_chain_opt o;
+  int stage = 1;
+  long long l_pac = 0;
+  const char *alt = nullptr;
+};
+
+// -mkchains: per read "l_query n_smems", then per SMEM "m n s c1 c2 ..."
+static int run_mkchains(const char *in_file, const char *out_file, const MkOpt &mo, const char *contigs) {
+  std::vector<int64_t> contig_end;
+  std::vector<uint8_t> is_alt;
+  for (const char *c = contigs; c && *c;) {
+    char *e = nullptr;
+    contig_end.push_back(strtoll(c, &e, 10));
+    if (e == c) {
+      fprintf(stderr, "bsw: -contigs expects e1,e2,...\n");
+      return 1;
+    }
+    c = *e == ',' ? e + 1 : e;
+  }
+  for (const char *c = mo.alt; c && *c;) {
+    char *e = nullptr;
+    is_alt.push_back((uint8_t)(strtol(c, &e, 10) != 0));
+    if (e == c) {
+      fprintf(stderr, "bsw: -alt expects a1,a2,...\n");
+      return 1;
+    }
+    c = *e == ',' ? e + 1 : e;
+  }
+  const size_t n_contigs = contig_end.empty() ? 1 : contig_end.size();
+  if (!is_alt.empty() && is_alt.size() != n_contigs) {
+    fprintf(stderr, "bsw: -alt has %zu entries for %zu contigs\n", is_alt.size(), n_contigs);
+    return 1;
+  }
+  const long long l_pac = mo.l_pac ? mo.l_pac : contig_end.empty() ? 0 : (long long)contig_end.back();
+  if (l_pac < 1) {
+    fprintf(stderr, "bsw: -mkchains needs -lpac <l_pac> or -contigs e1,e2,...\n");
+    return 1;
+  }
+  FILE *f = fopen(in_file, "r");
+  if (!f) {
+    fprintf(stderr, "Could not open file: %s\n", in_file);
+    return 1;
+  }
+  std::vector<int32_t> lq;
+  std::vector<gb_bsw_mem> mems;
+  std::vector<int64_t> coords;
+  // a line is read whole, whatever its length: an SMEM line carries up to max_occ coordinates
+  std::vector<char> piece(1 << 16);
+  std::string line;
+  auto read_line = [&]() -> bool {
+    line.clear();
+    while (fgets(piece.data(), (int)piece.size(), f)) {
+      line += piece.data();
+      if (!line.empty() && line.back() == '\n') break;
+    }
+    return !line.empty();
+  };
+  auto parse = [&]() -> int {
+    while (read_line()) {
+      long l = 0, nm = 0;
+      if (line[0] == '\n' || line[0] == '\r') continue;
+      if (sscanf(line.c_str(), "%ld %ld", &l, &nm) != 2 || nm < 0) {
+        fprintf(stderr, "read %zu: expected \"l_query n_smems\"\n", lq.size());
+        return 1;
+      }
+      for (long k = 0; k < nm; ++k) {
+        if (!read_line()) {
+          fprintf(stderr, "read %zu: %ld SMEM lines are missing\n", lq.size(), nm - k);
+          return 1;
+        }
+        const char *q = line.c_str();
+        char *e = nullptr;
+        long long v[3];
+        for (int j = 0; j < 3; ++j) {
+          v[j] = strtoll(q, &e, 10);
+          if (e == q) {
+            fprintf(stderr, "read %zu SMEM %ld: expected \"m n s c1 c2 ...\"\n", lq.size(), k);
+            return 1;
+          }
+          q = e;
+        }
+        gb_bsw_mem m;
+        memset(&m, 0, sizeof(m));
+        m.read = (int32_t)lq.size(), m.m = (int32_t)v[0], m.n = (int32_t)v[1], m.s = v[2];
+        for (;;) {
+          const long long c = strtoll(q, &e, 10);
+          if (e == q) break;
+          q = e;
+          coords.push_back(c);
+          ++m.n_coord;
+        }
+        while (*q == ' ' || *q == '\t' || *q == '\r' || *q == '\n') ++q;
+        if (*q) {
+          fprintf(stderr, "read %zu SMEM %ld: \"%.20s\" is not a coordinate\n", lq.size(), k, q);
+          return 1;
+        }
+        mems.push_back(m);
+      }
+      lq.push_back((int32_t)l);
+    }
+    return 0;
+  };
+  const int bad = parse();
+  fclose(f);
+  if (bad) return bad;
+  FILE *info = out_file ? stdout : stderr;
+  fprintf(info, "Number of input reads: %zu (%zu SMEMs, %zu coordinates)\n", lq.size(), mems.size(), coords.size());
+  const size_t cap = coords.size() ? coords.size() : 1;
+  std::vector<int64_t> rco(lq.size() + 1), cso(cap + 1);
+  std::vector<gb_bsw_seed> seeds(cap);
+  std::vector<gb_bsw_chain_info> ci(cap);
+  int64_t nc = 0, ns = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int st = gb_bsw_seeds2chains(&mo.o, mo.stage, l_pac, contig_end.empty() ? nullptr : contig_end.data(),
+                                     is_alt.empty() ? nullptr : is_alt.data(), (int64_t)contig_end.size(),
+                                     (int64_t)lq.size(), lq.data(), mems.data(), (int64_t)mems.size(), coords.data(),
+                                     (int64_t)coords.size(), rco.data(), cso.data(), seeds.data(), ci.data(),
+                                     (int64_t)coords.size(), (int64_t)coords.size(), &nc, &ns);
+  const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (st) {
+    fprintf(stderr, "gb_bsw_seeds2chains failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  int64_t host_reads = 0;
+  gb_bsw_seeds2chains_timing(nullptr, nullptr, nullptr, &host_reads);
+  fprintf(info, "Executed chaining of seeds (%s)...\n",
+          host_reads == (int64_t)lq.size() ? "host path" : "MI355X, gfx950");
+  fprintf(info, "Overall time = %0.3f s (%lld chains, %lld seeds incl. host<->device copies)\n", sw_s, (long long)nc,
+          (long long)ns);
+  fprintf(info, "Total reads processed: %zu\n", lq.size());
+  FILE *o = out_file ? fopen(out_file, "w") : stdout;
+  if (!o) {
+    fprintf(stderr, "Could not open file: %s\n", out_file);
+    return 1;
+  }
+  for (size_t r = 0; r < lq.size(); ++r)
+    for (int64_t c = rco[r]; c < rco[r + 1]; ++c) {
+      const gb_bsw_chain_info &x = ci[(size_t)c];
+      fprintf(o, "%zu\t%lld\t%d\t%d\t%d\t%d\t%lld", r, (long long)x.pos, x.rid, x.is_alt, x.w, x.kept,
+              (long long)(cso[(size_t)c + 1] - cso[(size_t)c]));
+      for (int64_t k = cso[(size_t)c]; k < cso[(size_t)c + 1]; ++k) {
+        const gb_bsw_seed &s = seeds[(size_t)k];
+        fprintf(o, "\t%d;%d;%d,%lld", s.score, s.len, s.qbeg, (long long)s.rbeg);
+      }
+      fputc('\n', o);
+    }
+  if (out_file) fclose(o);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
   const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr, *contigs = nullptr;
-  bool global = false, local = false, gencigar = false, chain2aln = false;
+  bool global = false, local = false, gencigar = false, chain2aln = false, mkchains = false;
   int band = 100, zdrop_arg = 100, clip5 = 5, clip3 = 5;
+  MkOpt mo;
+  gb_bsw_chain_default_opt(&mo.o);
   for (int i = 1; i < argc; i += 2) {
+    if (!strcmp(argv[i], "-mkchains")) {
+      mkchains = true;
+      --i;
+      continue;
+    }
     if (!strcmp(argv[i], "-chain2aln")) {
       chain2aln = true;
       --i;
       continue;
     }
-    if (argv[i][0] != '-') {  // -chain2aln's input file may stand alone
+    if (argv[i][0] != '-') {  // -chain2aln's and -mkchains' input file may stand alone
       pair_file = argv[i];
       --i;
       continue;
@@ -264,7 +432,17 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-pairs")) pair_file = argv[i + 1];
     else if (!strcmp(argv[i], "-pac")) pac_file = argv[i + 1];
     else if (!strcmp(argv[i], "-contigs")) contigs = argv[i + 1];
-    else if (!strcmp(argv[i], "-w")) band = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-w")) band = mo.o.w = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-lpac")) mo.l_pac = atoll(argv[i + 1]);
+    else if (!strcmp(argv[i], "-alt")) mo.alt = argv[i + 1];
+    else if (!strcmp(argv[i], "-stage")) mo.stage = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-maxgap")) mo.o.max_chain_gap = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-maxocc")) mo.o.max_occ = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-minseed")) mo.o.min_seed_len = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-minweight")) mo.o.min_chain_weight = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-maxextend")) mo.o.max_chain_extend = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-mask")) mo.o.mask_level = (float)atof(argv[i + 1]);
+    else if (!strcmp(argv[i], "-drop")) mo.o.drop_ratio = (float)atof(argv[i + 1]);
     else if (!strcmp(argv[i], "-zdrop")) zdrop_arg = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-clip5")) clip5 = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-clip3")) clip3 = atoi(argv[i + 1]);
@@ -281,6 +459,13 @@ int main(int argc, char **argv) {
   if (global && local) {
     fprintf(stderr, "bsw: -local and -global exclude each other\n");
     return 1;
+  }
+  if (mkchains) {
+    if (global || local || gencigar || chain2aln) {
+      fprintf(stderr, "bsw: -mkchains excludes -global, -local, -gencigar and -chain2aln\n");
+      return 1;
+    }
+    return run_mkchains(pair_file, out_file, mo, contigs);
   }
   if (chain2aln) {
     if (global || local || gencigar) {

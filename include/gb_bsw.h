@@ -240,7 +240,8 @@ int gb_bsw_local_timing(float *kernel_ms);
 
 /* ---- seed extension from chains: all of bwa's mem_chain2aln (tools/bwa/bwamem.c:632-824) over a
  * device-resident packed reference. In go the seeds an SA lookup produces, grouped into chains and the
- * chains into reads; out come the alignment regions mem_chain2aln would push, bit for bit, in its order:
+ * chains into reads (gb_bsw_seeds2chains, below, does that); out come the alignment regions
+ * mem_chain2aln would push, bit for bit, in its order:
  * the chains of a read in the order given into one region list (mem_align1_core passes the same regs for
  * every chain of a read), the seeds of a chain by decreasing score << 32 | index. rb, re, qb, qe, truesc
  * and w are what gb_bsw_gen_cigar_retry consumes. rid, frac_rep and everything after mem_chain2aln
@@ -310,6 +311,81 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
  * 2 w, [2] right at w, [3] right at 2 w (0 for a round that had no seed and launched nothing); the finish
  * kernel; the filter, scan and emit kernels. */
 int gb_bsw_chain2aln_timing(float *gather_ms, float ext_ms[4], float *finish_ms, float *filter_ms);
+
+/* ---- chains from seeds: bwa's mem_chain after mem_collect_intv (tools/bwa/bwamem.c:265-310, with
+ * test_and_merge :190-211, bns_intv2rid / bns_pos2rid bntseq.c:355-379 and kbtree.h at t = 5) and
+ * mem_chain_flt (:327-385, with mem_chain_weight :213-232 and ks_introsort ksort.h:176-226), bit for bit
+ * and in the reference's order. In go the SMEMs of gb_fmi_results and the coordinates of
+ * gb_fmi_sa_entries, unchanged; out come the CSR arguments of gb_bsw_chain2aln.
+ *
+ * mems are grouped by read in read order, in any order within a read; the call puts each read's SMEMs
+ * into mem_chain's order (m << 32 | n + 1 ascending; equal keys are the same substring and interval) and
+ * each SMEM's coordinates move with it. coords holds the coordinates concatenated in SMEM order, n_coord
+ * of them per SMEM: what mem_chain's loop takes for that s and max_occ (step = s > max_occ ? s / max_occ
+ * : 1; rows k, k + step, ... below s, at most max_occ). contig_end / n_contigs as in gb_bsw_chain2aln
+ * (NULL: one contig), contig_is_alt (may be NULL: none) one byte per contig.
+ *
+ * stage 0 returns mem_chain's output: per read the chains in the B-tree's in-order traversal, each
+ * chain's seeds in insertion order (score == len), info with pos, rid, is_alt, l_rep, frac_rep and w =
+ * kept = 0. stage 1 additionally applies mem_chain_flt: the chains in the order the filter leaves them
+ * (by weight as ks_introsort leaves ties, kept == 0 removed), info.w the weight and info.kept 1, 2 or 3.
+ * mem_flt_chained_seeds (:598-615) is not applied: the call refuses a read with SMEMs and l_query >=
+ * min_seed_len for which it would not be the identity, i.e. unless min_l > MEM_SEEDSW_COEF * l_query in
+ * the reference's types (min_l = 1.1f * min_chain_weight, or 5.5f * log(l_query) when that is 0).
+ *
+ * read_chain_off has n_reads + 1 entries, chain_seed_off chains + 1. n_coords always suffices for
+ * chain_cap and seed_cap. With a smaller cap that does not suffice the call returns GB_ERR_ARG, sets
+ * *chains_used and *seeds_used (may be NULL) to the counts needed, fills read_chain_off (and
+ * chain_seed_off when chain_cap suffices) and leaves seeds[] and info[] untouched.
+ *
+ * Refused for the whole call with GB_ERR_ARG before any device work, nothing written, the read or SMEM
+ * named in gb_last_error(): read decreasing or outside [0, n_reads); m < 0, n < m, n >= l_query, s < 1;
+ * n_coord not the number above; the sum of n_coord != n_coords; a coordinate outside [0, 2 l_pac);
+ * max_occ < 1, w < 0, max_chain_gap < 0, max_chain_extend < 1; mask_level or drop_ratio not finite;
+ * contig_end not increasing or not ending at l_pac; stage not 0 or 1; 2^31 coordinates or more; the
+ * mem_flt_chained_seeds case above. n_reads == 0 succeeds without a device.
+ *
+ * The chains are built on the device, one read per lane. GB_BSW_MKCHAIN_HOST=1 sends every read through
+ * the library's host path instead (no device is touched; GB_BSW_MKCHAIN_THREADS host threads, a number
+ * from 1 up, default up to 16; anything else is refused), and a read with more than
+ * GB_BSW_MKCHAIN_DEV_COORDS coordinates takes it in any case: a read has at most as many chains as
+ * coordinates, so every read of up to that many chains stays on the device. Equal-pos ties are no reason
+ * for the host path. An environment variable of the same name overrides the bound (a count from 0 up;
+ * the tests reach a call served by both paths with it). No exception leaves the call: running out of
+ * host memory returns GB_ERR_NOMEM. */
+#define GB_BSW_MKCHAIN_DEV_COORDS 65536
+
+typedef struct gb_bsw_chain_opt { /* the mem_opt_t fields mem_chain / mem_chain_flt read */
+  int32_t w, max_chain_gap, max_occ, min_seed_len, min_chain_weight, max_chain_extend;
+  float mask_level, drop_ratio;
+} gb_bsw_chain_opt;
+/* 100, 10000, 500, 19, 0, 1 << 30, 0.50f, 0.50f (bwamem.c:50-86) */
+void gb_bsw_chain_default_opt(gb_bsw_chain_opt *o);
+
+typedef struct gb_bsw_mem { /* one SMEM of one read, 24 bytes */
+  int32_t read, m, n; /* gb_smem's rid, m, n: the seed is query [m, n] inclusive */
+  int32_t n_coord;    /* coordinates it owns (counts[i] of gb_fmi_sa_entries) */
+  int64_t s;          /* interval size */
+} gb_bsw_mem;
+
+typedef struct gb_bsw_chain_info { /* one per output chain, 32 bytes */
+  int64_t pos;
+  int32_t rid, is_alt, w, kept; /* w, kept: 0 at stage 0 */
+  int32_t l_rep;
+  float frac_rep; /* (float)l_rep / l_query */
+} gb_bsw_chain_info;
+
+int gb_bsw_seeds2chains(const gb_bsw_chain_opt *opt, int32_t stage, int64_t l_pac, const int64_t *contig_end,
+                        const uint8_t *contig_is_alt, int64_t n_contigs, int64_t n_reads, const int32_t *l_query,
+                        const gb_bsw_mem *mems, int64_t n_mems, const int64_t *coords, int64_t n_coords,
+                        int64_t *read_chain_off, int64_t *chain_seed_off, gb_bsw_seed *seeds, gb_bsw_chain_info *info,
+                        int64_t chain_cap, int64_t seed_cap, int64_t *chains_used, int64_t *seeds_used);
+
+/* Of the calling thread's last gb_bsw_seeds2chains: the device time of the build kernel, the filter kernel
+ * and the emit group (count, scans, scatter), 0 for a call that ran on the host alone, and the number of
+ * reads that took the host path. emit_ms is the span between two events around the group, so it includes
+ * the one read-back inside it (the chain count, which sizes the second scan) and the host's wait for it. */
+int gb_bsw_seeds2chains_timing(float *build_ms, float *filter_ms, float *emit_ms, int64_t *host_reads);
 
 #ifdef __cplusplus
 }
