@@ -17,7 +17,7 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle mkchain-sanitize
+.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -93,6 +93,18 @@ tests/_build/mkchain_host_check: tests/cpp/mkchain_host_check.cpp $(CSRC)/bsw_mk
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_mkchain.hip \
 	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the same for gb_bsw_finish_regs: its source file, the two it calls into (the packed reference and the
+# band rule) and the common one. The call runs on the host and the program touches no device. Not part of
+# `all`.
+REGS_CHECK_SRCS := $(CSRC)/bsw_regs.hip $(CSRC)/bsw_gencigar.hip $(CSRC)/bsw_global.hip $(CSRC)/gb_common.cpp
+regs-sanitize: tests/_build/regs_host_check
+	tests/_build/regs_host_check
+tests/_build/regs_host_check: tests/cpp/regs_host_check.cpp $(REGS_CHECK_SRCS) $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(REGS_CHECK_SRCS) \
+	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:
 	$(MAKE) -s -C oracle all

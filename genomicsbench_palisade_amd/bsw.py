@@ -673,3 +673,111 @@ def seeds2chains_timing():
     check(_decl_mkchain().gb_bsw_seeds2chains_timing(*[ctypes.byref(x) for x in t], ctypes.byref(h)),
           "gb_bsw_seeds2chains_timing")
     return t[0].value, t[1].value, t[2].value, h.value
+
+
+# ---- from regions to primaries (mem_sort_dedup_patch, mem_mark_primary_se, MAPQ; bwamem.c:406-558, 993-1041) ----
+
+# gb_bsw_alnreg (include/gb_bsw.h): mem_alnreg_t's fields plus mapq
+ALNREG_DTYPE = np.dtype([("rb", "<i8"), ("re", "<i8")] + [(k, "<i4") for k in (
+    "qb", "qe", "rid", "score", "truesc", "sub", "alt_sc", "csub", "sub_n", "w", "seedcov", "secondary",
+    "secondary_all", "seedlen0", "n_comp", "is_alt")] + [("frac_rep", "<f4"), ("mapq", "<i4"), ("hash", "<u8")])
+assert ALNREG_DTYPE.itemsize == 96
+ALNREG_FIELDS = ALNREG_DTYPE.names
+
+
+class RegOpt(ctypes.Structure):
+    """gb_bsw_reg_opt: the mem_opt_t fields mem_sort_dedup_patch, mem_mark_primary_se, mem_reorder_primary5 and
+    mem_approx_mapq_se read."""
+    _fields_ = ([(k, ctypes.c_int32) for k in "a b o_del e_del o_ins e_ins w max_chain_gap min_seed_len".split()]
+                + [(k, ctypes.c_float) for k in "mask_level mask_level_redun mapQ_coef_len".split()]
+                + [(k, ctypes.c_int32) for k in "mapQ_coef_fac T primary5".split()])
+
+
+_REG_OPT_FLOATS = ("mask_level", "mask_level_redun", "mapQ_coef_len")
+
+
+def _decl_regs():
+    L = _decl_mkchain()
+    if getattr(L, "_bsw_regs_decl", False):
+        return L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    L.gb_bsw_reg_default_opt.argtypes = [vp]
+    L.gb_bsw_reg_default_opt.restype = None
+    L.gb_bsw_finish_regs.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp]
+    L.gb_bsw_alnreg_from_regions.argtypes = [vp, i64, vp, i64, vp]
+    L.gb_bsw_finish_regs_timing.argtypes = [vp] * 6
+    L._bsw_regs_decl = True
+    return L
+
+
+def reg_opt(**kw):
+    """bwa's defaults (bwamem.c:50-86): a 1, b 4, gaps 6 / 1, w 100, max_chain_gap 10000, min_seed_len 19,
+    mask_level 0.5, mask_level_redun 0.95, mapQ_coef_len 50, mapQ_coef_fac 3, T 30, primary5 0; keywords
+    override."""
+    o = RegOpt()
+    _decl_regs().gb_bsw_reg_default_opt(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, float(v) if k in _REG_OPT_FLOATS else int(v))
+    return o
+
+
+def alnregs_from_regions(regions, chain_info):
+    """gb_bsw_alnreg_from_regions: ALNREG_DTYPE records from gb_bsw_chain2aln's regions and
+    gb_bsw_seeds2chains' info (rid and frac_rep through regions["chain"])."""
+    regions = np.ascontiguousarray(regions, REGION_DTYPE)
+    info = np.ascontiguousarray(chain_info, CHAIN_INFO_DTYPE)
+    out = np.zeros(len(regions), ALNREG_DTYPE)
+    check(_decl_regs().gb_bsw_alnreg_from_regions(_buf(regions), len(regions), _buf(info), len(info), _buf(out)),
+          "gb_bsw_alnreg_from_regions")
+    return out
+
+
+def alnregs_from_chain2aln(c2a_result, chains_result):
+    """The output of chain2aln_csr and of seeds2chains as the (reg_off, regs) arguments of finish_regs."""
+    n_reg = np.asarray(c2a_result["n_reg"], np.int64)
+    reg_off = np.concatenate([[0], np.cumsum(n_reg)]).astype(np.int64)
+    return reg_off, alnregs_from_regions(c2a_result["regs"], chains_result["info"])
+
+
+def finish_regs_raw(ref, qbuf, idq, l_query, reg_off, regs, opt=None, params=None, stage=1, id0=0, contig_is_alt=None,
+                    n_contigs=None):
+    """gb_bsw_finish_regs without the status check: (status, regs, n_out); regs is a copy the call worked on
+    in place (a refused call leaves it equal to the input)."""
+    opt = opt if opt is not None else reg_opt()
+    params = params if params is not None else default_params()
+    qbuf = np.ascontiguousarray(qbuf, np.uint8)
+    idq = np.ascontiguousarray(idq, np.int64)
+    l_query = np.ascontiguousarray(l_query, np.int32)
+    reg_off = np.ascontiguousarray(reg_off, np.int64)
+    regs = np.array(regs, ALNREG_DTYPE, copy=True, order="C")
+    n = len(idq)
+    alt = None if contig_is_alt is None else np.ascontiguousarray(contig_is_alt, np.uint8)
+    nc = (len(alt) if alt is not None else 1) if n_contigs is None else int(n_contigs)
+    n_out = np.full(max(n, 1), -1, np.int32)
+    st = _decl_regs().gb_bsw_finish_regs(
+        ctypes.byref(params), ctypes.byref(opt), int(stage), ref.h, None if alt is None else alt.ctypes.data, nc,
+        _buf(qbuf), len(qbuf), n, _buf(idq), _buf(l_query), int(id0), _buf(reg_off), _buf(regs), n_out.ctypes.data)
+    return st, regs, n_out[:n]
+
+
+def finish_regs(ref, qbuf, idq, l_query, reg_off, regs, **kw):
+    """gb_bsw_finish_regs: per read mem_sort_dedup_patch (stage=0) and then mem_mark_primary_se,
+    mem_reorder_primary5 (opt.primary5) and the MAPQ (stage=1, the default). reg_off has one entry per read
+    plus one, regs is an ALNREG_DTYPE array. Keywords: opt (reg_opt()), params (mat), stage, id0,
+    contig_is_alt, n_contigs. Returns (regs, n_out): read r's survivors are regs[reg_off[r]:reg_off[r] +
+    n_out[r]], the rest of its slots zero. The call runs on the host and reads ref's host copy, which a
+    device call on the same Ref releases: give it a Ref of its own."""
+    st, out, n_out = finish_regs_raw(ref, qbuf, idq, l_query, reg_off, regs, **kw)
+    check(st, "gb_bsw_finish_regs")
+    return out, n_out
+
+
+def finish_regs_timing():
+    """(dedup_ms, dp_ms, mark_ms, dp_rounds, dp_requests, host_reads) of this thread's last finish_regs: the
+    three device times are 0 (the call runs on the host), dp_rounds is the largest number of merge alignments
+    one read needed, dp_requests their total."""
+    t = [ctypes.c_float() for _ in range(3)]
+    r, q, h = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_decl_regs().gb_bsw_finish_regs_timing(*[ctypes.byref(x) for x in t], ctypes.byref(r), ctypes.byref(q),
+                                                ctypes.byref(h)), "gb_bsw_finish_regs_timing")
+    return t[0].value, t[1].value, t[2].value, r.value, q.value, h.value

@@ -394,10 +394,119 @@ static int run_mkchains(const char *in_file, const char *out_file, const MkOpt &
   return 0;
 }
 
+struct RegsOpt {
+  int stage = 1, primary5 = 0;
+  long long id0 = 0;
+  float redun = 0.95f;
+};
+
+// -finishregs: per read "bases n_regions", then per region thirteen numbers
+static int run_finishregs(const char *pac_file, const char *in_file, const char *out_file, const gb_bsw_params &gp,
+                          const gb_bsw_reg_opt &ro, const RegsOpt &xo, const char *alt, const char *contigs) {
+  gb_ref *ref = nullptr;
+  int st = gb_ref_load_pac(pac_file, &ref);
+  if (st) {
+    fprintf(stderr, "gb_ref_load_pac failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  std::vector<uint8_t> is_alt;
+  for (const char *c = alt; c && *c;) {
+    char *e = nullptr;
+    is_alt.push_back((uint8_t)(strtol(c, &e, 10) != 0));
+    if (e == c) {
+      fprintf(stderr, "bsw: -alt expects a1,a2,...\n");
+      return 1;
+    }
+    c = *e == ',' ? e + 1 : e;
+  }
+  int64_t n_contigs = (int64_t)is_alt.size();
+  if (!n_contigs && contigs && *contigs) {
+    n_contigs = 1;
+    for (const char *c = contigs; *c; ++c) n_contigs += *c == ',';
+  }
+  FILE *f = fopen(in_file, "r");
+  if (!f) {
+    fprintf(stderr, "Could not open file: %s\n", in_file);
+    return 1;
+  }
+  std::vector<uint8_t> qer;
+  std::vector<int64_t> idq, reg_off(1, 0);
+  std::vector<int32_t> lq;
+  std::vector<gb_bsw_alnreg> regs;
+  std::vector<char> line(1 << 12);
+  int max_rid = 0;
+  while (fgets(line.data(), (int)line.size(), f)) {
+    if (line[0] == '\n' || line[0] == '\r') continue;
+    size_t n = 0;
+    while (line[n] >= '0' && line[n] <= '4') ++n;
+    long nr = -1;
+    if (n < 1 || sscanf(line.data() + n, "%ld", &nr) != 1 || nr < 0) {
+      fprintf(stderr, "read %zu: expected \"bases n_regions\"\n", lq.size());
+      return 1;
+    }
+    idq.push_back((int64_t)qer.size());
+    lq.push_back((int32_t)n);
+    for (size_t k = 0; k < n; ++k) qer.push_back((uint8_t)(line[k] - 48));
+    for (long k = 0; k < nr; ++k) {
+      gb_bsw_alnreg a;
+      memset(&a, 0, sizeof(a));
+      long long rb = 0, re = 0;
+      if (!fgets(line.data(), (int)line.size(), f) ||
+          sscanf(line.data(), "%lld %lld %d %d %d %d %d %d %d %d %d %d %f", &rb, &re, &a.qb, &a.qe, &a.rid, &a.score,
+                 &a.truesc, &a.w, &a.seedcov, &a.seedlen0, &a.csub, &a.sub_n, &a.frac_rep) != 13) {
+        fprintf(stderr, "read %zu region %ld: expected thirteen numbers\n", lq.size() - 1, k);
+        return 1;
+      }
+      a.rb = rb, a.re = re;
+      max_rid = a.rid > max_rid ? a.rid : max_rid;
+      regs.push_back(a);
+    }
+    reg_off.push_back((int64_t)regs.size());
+  }
+  fclose(f);
+  if (!n_contigs) n_contigs = (int64_t)max_rid + 1;
+  FILE *info = out_file ? stdout : stderr;
+  fprintf(info, "Number of input reads: %zu (%zu regions)\n", lq.size(), regs.size());
+  std::vector<int32_t> n_out(lq.size() + 1);
+  const auto t0 = std::chrono::steady_clock::now();
+  st = gb_bsw_finish_regs(&gp, &ro, xo.stage, ref, is_alt.empty() ? nullptr : is_alt.data(), n_contigs, qer.data(),
+                          (int64_t)qer.size(), (int64_t)lq.size(), idq.data(), lq.data(), xo.id0, reg_off.data(),
+                          regs.data(), n_out.data());
+  const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (st) {
+    fprintf(stderr, "gb_bsw_finish_regs failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  int32_t rounds = 0;
+  int64_t reqs = 0, host_reads = 0, left = 0;
+  gb_bsw_finish_regs_timing(nullptr, nullptr, nullptr, &rounds, &reqs, &host_reads);
+  for (size_t r = 0; r < lq.size(); ++r) left += n_out[r];
+  fprintf(info, "Executed region dedup, primary marking and MAPQ (on the host, %lld reads)...\n", (long long)host_reads);
+  fprintf(info, "Overall time = %0.3f s (%lld regions left, %lld merge alignments, at most %d for one read)\n", sw_s,
+          (long long)left, (long long)reqs, rounds);
+  fprintf(info, "Total reads processed: %zu\n", lq.size());
+  FILE *o = out_file ? fopen(out_file, "w") : stdout;
+  if (!o) {
+    fprintf(stderr, "Could not open file: %s\n", out_file);
+    return 1;
+  }
+  for (size_t r = 0; r < lq.size(); ++r)
+    for (int32_t k = 0; k < n_out[r]; ++k) {
+      const gb_bsw_alnreg &a = regs[(size_t)reg_off[r] + (size_t)k];
+      fprintf(o, "%zu\t%lld\t%lld\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", r,
+              (long long)a.rb, (long long)a.re, a.qb, a.qe, a.rid, a.score, a.truesc, a.sub, a.alt_sc, a.csub, a.sub_n, a.w,
+              a.seedcov, a.secondary, a.secondary_all, a.seedlen0, a.n_comp, a.is_alt, a.mapq);
+    }
+  if (out_file) fclose(o);
+  gb_ref_destroy(ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
   const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr, *contigs = nullptr;
-  bool global = false, local = false, gencigar = false, chain2aln = false, mkchains = false;
+  bool global = false, local = false, gencigar = false, chain2aln = false, mkchains = false, finishregs = false;
+  RegsOpt xo;
   int band = 100, zdrop_arg = 100, clip5 = 5, clip3 = 5;
   MkOpt mo;
   gb_bsw_chain_default_opt(&mo.o);
@@ -412,7 +521,12 @@ int main(int argc, char **argv) {
       --i;
       continue;
     }
-    if (argv[i][0] != '-') {  // -chain2aln's and -mkchains' input file may stand alone
+    if (!strcmp(argv[i], "-finishregs")) {
+      finishregs = true;
+      --i;
+      continue;
+    }
+    if (argv[i][0] != '-') {  // -chain2aln's, -mkchains' and -finishregs' input file may stand alone
       pair_file = argv[i];
       --i;
       continue;
@@ -435,7 +549,10 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-w")) band = mo.o.w = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-lpac")) mo.l_pac = atoll(argv[i + 1]);
     else if (!strcmp(argv[i], "-alt")) mo.alt = argv[i + 1];
-    else if (!strcmp(argv[i], "-stage")) mo.stage = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-stage")) mo.stage = xo.stage = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-id0")) xo.id0 = atoll(argv[i + 1]);
+    else if (!strcmp(argv[i], "-redun")) xo.redun = (float)atof(argv[i + 1]);
+    else if (!strcmp(argv[i], "-primary5")) xo.primary5 = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-maxgap")) mo.o.max_chain_gap = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-maxocc")) mo.o.max_occ = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-minseed")) mo.o.min_seed_len = atoi(argv[i + 1]);
@@ -459,6 +576,25 @@ int main(int argc, char **argv) {
   if (global && local) {
     fprintf(stderr, "bsw: -local and -global exclude each other\n");
     return 1;
+  }
+  if (finishregs) {
+    if (global || local || gencigar || chain2aln || mkchains) {
+      fprintf(stderr, "bsw: -finishregs excludes -global, -local, -gencigar, -chain2aln and -mkchains\n");
+      return 1;
+    }
+    if (!pac_file) {
+      fprintf(stderr, "bsw: -finishregs needs -pac <file.pac>\n");
+      return 1;
+    }
+    gb_bsw_params gp;
+    gb_bsw_default_params(&gp);
+    gb_bsw_fill_scmat(w_match, w_mismatch, w_ambig, gp.mat);
+    gb_bsw_reg_opt ro;
+    gb_bsw_reg_default_opt(&ro);
+    ro.a = w_match, ro.b = w_mismatch, ro.o_del = ro.o_ins = w_open, ro.e_del = ro.e_ins = w_extend;
+    ro.w = band, ro.max_chain_gap = mo.o.max_chain_gap, ro.min_seed_len = mo.o.min_seed_len;
+    ro.mask_level = mo.o.mask_level, ro.mask_level_redun = xo.redun, ro.primary5 = xo.primary5;
+    return run_finishregs(pac_file, pair_file, out_file, gp, ro, xo, mo.alt, contigs);
   }
   if (mkchains) {
     if (global || local || gencigar || chain2aln) {

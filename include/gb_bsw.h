@@ -244,8 +244,9 @@ int gb_bsw_local_timing(float *kernel_ms);
  * mem_chain2aln would push, bit for bit, in its order:
  * the chains of a read in the order given into one region list (mem_align1_core passes the same regs for
  * every chain of a read), the seeds of a chain by decreasing score << 32 | index. rb, re, qb, qe, truesc
- * and w are what gb_bsw_gen_cigar_retry consumes. rid, frac_rep and everything after mem_chain2aln
- * (mem_sort_dedup_patch and on) stay with the caller.
+ * and w are what gb_bsw_gen_cigar_retry consumes. rid and frac_rep come from the chain
+ * (gb_bsw_alnreg_from_regions joins them); what follows mem_chain2aln, mem_sort_dedup_patch up to the MAPQ,
+ * is gb_bsw_finish_regs, below.
  *
  * params gives mat, the gap penalties, zdrop and w = opt->w; params->end_bonus is ignored: left
  * extensions pass pen_clip5 as ksw_extend2's end_bonus, right extensions pen_clip3. contig_end (may be
@@ -386,6 +387,89 @@ int gb_bsw_seeds2chains(const gb_bsw_chain_opt *opt, int32_t stage, int64_t l_pa
  * reads that took the host path. emit_ms is the span between two events around the group, so it includes
  * the one read-back inside it (the chain count, which sizes the second scan) and the host's wait for it. */
 int gb_bsw_seeds2chains_timing(float *build_ms, float *filter_ms, float *emit_ms, int64_t *host_reads);
+
+/* ---- from regions to primaries: what bwa does with a read's regions between mem_chain2aln and
+ * mem_reg2aln's re-banding loop (tools/bwa/bwamem.c), bit for bit and in the reference's order, for a batch
+ * of single-end reads.
+ *
+ * stage 0 is the tail of mem_align1_core (:1114-1126): mem_sort_dedup_patch (:437-489) with mem_patch_reg
+ * (:406-435) and its score-only global alignments (bwa_gen_cigar2 without a CIGAR, bwa.c:121-167), then is_alt
+ * becomes 1 for a region on an ALT contig (the reference leaves it as given otherwise). A read with fewer
+ * than two regions is returned as it came (n_comp included), as the reference's early return leaves it.
+ * stage 1 adds the single-end worker's steps (:1235-1236): mem_mark_primary_se (:521-558, hash =
+ * hash_64(id0 + read index + i), utils.h:98), mem_reorder_primary5 (:1019-1041) when opt->primary5 is set,
+ * and mapq = secondary < 0 ? mem_approx_mapq_se (:993-1017) : 0, the value mem_reg2aln assigns (:1147).
+ * At stage 0 mapq is 0 and secondary, secondary_all, alt_sc and hash are left as given.
+ *
+ * sub, csub and sub_n are inputs as well as outputs: a merge takes the larger sub and csub, csub feeds the
+ * MAPQ, and the reference never resets sub_n, so stage 1 adds to what is there (twice for a hit counted by
+ * both passes of mem_mark_primary_se_core). Regions from gb_bsw_chain2aln carry 0 in all three.
+ *
+ * mem_reg2sam's selection loop (T, drop_ratio, the supplementary MAPQ cap), XA, infer_bw, the SAM text and
+ * everything paired-end stay with the caller. The stage-1 primaries go into gb_bsw_gen_cigar_retry as they
+ * are (rb, re, qb, qe, w, truesc).
+ *
+ * params gives mat; the gap penalties of mem_patch_reg's alignment are opt's, as in the reference.
+ * Read r has the query seq_buf_qer[idq[r] .. idq[r] + l_query[r]) and the regions regs[reg_off[r] ..
+ * reg_off[r + 1]). The result is written in place: the survivors of read r are regs[reg_off[r] ..
+ * reg_off[r] + n_out[r]) in the reference's final order and the read's remaining slots are zeroed.
+ * contig_is_alt (may be NULL: none) has one byte per contig; n_contigs bounds rid in either case.
+ *
+ * Refused for the whole call with GB_ERR_ARG before any work, nothing written, the read or region
+ * named in gb_last_error(): stage not 0 or 1; offsets that decrease or do not start at 0; l_query outside
+ * [1, GB_BSW_MAX_QLEN] or a query outside seq_buf_qer on a read that has regions; a region without
+ * 0 <= qb < qe <= l_query or 0 <= rb < re <= 2 l_pac, or one bridging l_pac; rid outside [0, n_contigs);
+ * score < 1; seedcov < 1; sub, csub or sub_n < 0; w outside [0, 2^28) (a region's or opt's);
+ * max_chain_gap < 0; a < 1 or a + b < 1 (the MAPQ divides by both) or either at 32768 or above; |min_seed_len|
+ * at 32768 or above; n_contigs < 1; mask_level, mask_level_redun or mapQ_coef_len not finite; gap penalties
+ * outside [0, 32768) or an extension penalty of 0; 2^31 regions or more. One refusal is found during the
+ * work: a mem_patch_reg alignment whose target b.re - a.rb exceeds GB_BSW_GLOBAL_MAX_TLEN fails the call
+ * with GB_ERR_ARG naming the read; regs is untouched then too, because the library works on a copy and
+ * writes the caller's arrays only at the end. n_reads == 0 succeeds. No exception leaves the call
+ * (GB_ERR_NOMEM).
+ *
+ * The call runs on the host (GB_BSW_REGS_THREADS threads, a number from 1 up, default up to 16; anything
+ * else is refused) and touches no device: the per-read routines are written for one read per lane, with
+ * the alignment handed out as a request and the read resumed with its score, but the kernels around them
+ * are not part of the library yet ("bsw (regions to primaries)"). The alignments are a plain
+ * banded DP over the reference's host copy. That copy is released at the first device use of ref
+ * (gb_bsw_gen_cigar, gb_bsw_chain2aln, gb_ref_fetch): a call with a read of two regions or more then
+ * returns GB_ERR_ARG and says so, so a caller that runs those stages keeps a second gb_ref for this one. */
+typedef struct gb_bsw_alnreg { /* mem_alnreg_t's fields (bwamem.h:60-78) plus mapq, 96 bytes */
+  int64_t rb, re;
+  int32_t qb, qe, rid, score, truesc, sub, alt_sc, csub, sub_n, w, seedcov;
+  int32_t secondary, secondary_all, seedlen0, n_comp, is_alt;
+  float frac_rep;
+  int32_t mapq; /* out */
+  uint64_t hash;
+} gb_bsw_alnreg;
+
+typedef struct gb_bsw_reg_opt { /* the mem_opt_t fields these functions read */
+  int32_t a, b, o_del, e_del, o_ins, e_ins, w, max_chain_gap, min_seed_len;
+  float mask_level, mask_level_redun, mapQ_coef_len;
+  int32_t mapQ_coef_fac; /* an int in the reference: log(50) truncated */
+  int32_t T, primary5;   /* primary5: MEM_F_PRIMARY5 */
+} gb_bsw_reg_opt;
+/* 1, 4, 6, 1, 6, 1, 100, 10000, 19, 0.50f, 0.95f, 50.f, 3, 30, 0 (bwamem.c:50-86) */
+void gb_bsw_reg_default_opt(gb_bsw_reg_opt *o);
+
+int gb_bsw_finish_regs(const gb_bsw_params *params, const gb_bsw_reg_opt *opt, int32_t stage, const gb_ref *ref,
+                       const uint8_t *contig_is_alt, int64_t n_contigs, const uint8_t *seq_buf_qer, int64_t qer_bytes,
+                       int64_t n_reads, const int64_t *idq, const int32_t *l_query, int64_t id0, const int64_t *reg_off,
+                       gb_bsw_alnreg *regs, int32_t *n_out);
+
+/* The join between gb_bsw_chain2aln / gb_bsw_seeds2chains and gb_bsw_finish_regs: out[k] takes rb, re, qb,
+ * qe, score, truesc, w, seedcov and seedlen0 from regions[k], rid and frac_rep from
+ * chain_info[regions[k].chain], and 0 everywhere else. GB_ERR_ARG for a chain index outside [0, n_chains). */
+int gb_bsw_alnreg_from_regions(const gb_bsw_region *regions, int64_t n, const gb_bsw_chain_info *chain_info,
+                               int64_t n_chains, gb_bsw_alnreg *out);
+
+/* Of the calling thread's last gb_bsw_finish_regs: three device times, 0 while the call runs on the host
+ * (kept so that the signature need not change when kernels arrive: dedup, alignments, mark); the largest
+ * number of alignments one read needed (the rounds a one-read-per-lane device path would take), the number
+ * of alignments, and the reads served on the host (all of them). */
+int gb_bsw_finish_regs_timing(float *dedup_ms, float *dp_ms, float *mark_ms, int32_t *dp_rounds, int64_t *dp_requests,
+                              int64_t *host_reads);
 
 #ifdef __cplusplus
 }
