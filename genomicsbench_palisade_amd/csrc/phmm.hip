@@ -51,7 +51,8 @@ constexpr int kWave = 64;
 constexpr int kLdsHaplen = 9400;
 constexpr int kMaxHaplen = 65535;
 constexpr int kBndPad = 72;  // boundary records beyond column C (see phmm_stripe reads)
-constexpr int kRecPad = 4;   // boundary records below column 0 (lane 63's writes start at column -2)
+constexpr int kRecPad = 16;  // boundary records below column 0 (phmm_stripe's lane 63 writes from column -2 on,
+                             // phmm_rolled's from column -(kRollGroup - 1))
 constexpr int kQualTab = 128;
 constexpr int kStackRows = 2048;  // rows per stack (a testcase taller than this gets its own)
 // the batch's device counter words (d_count): [0..7] the passes' counters, then the f64 plan's
@@ -403,13 +404,249 @@ __device__ __forceinline__ int scan_add(int v) {  // wave-wide inclusive prefix 
   return v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Rolled stripes. A 64-row stripe costs C + 63 wave steps for 64 x C cells: the anti-diagonal fill.
+// Here the wave does not wait for lane 63 before it starts the next 64 rows ("turn"): lanes move on
+// in groups of kRollGroup at 4-step block boundaries. With P = roundup4(C + kRollGroup + 1) the
+// period of a turn, group k (lanes k*G .. k*G + G - 1) moves from turn s - 1 to turn s at step
+// s*P + k*G, and lane l of turn s is at column t - l - s*P at step t: every lane stays one column
+// behind the lane above it, so phmm_step and its two DPP shifts are unchanged. A group's last lane
+// has passed column C + 1 when the group moves on, so the lane below it has consumed its column-C
+// outputs; between column C and its switch a lane computes garbage columns (code 0), as a lane of
+// phmm_stripe does beyond column C, and after the switch its negative columns give zeros through
+// the column codes 6 and 5. A switch replaces the lane's RowParams and state by the next turn's,
+// which are computed for all 64 lanes at once (the per-stripe set-up code) when the last group has
+// moved, into a second register set. Lane 0 passes through column 0 itself, so it needs no special
+// initial state and takes the record of column 0 like any other.
+// Records: lane 63 writes its row's z / w in place at its column, lane 0 reads the row above at its
+// own; lane 0 reads column c P - 63 steps after lane 63 wrote it (4 records are fetched a block
+// ahead: P >= 72, given by C >= 64) and lane 63 overwrites it 63 steps after that. Both go through
+// one per-lane address register: every lane holds lane 0's read address, lane 63 its own write
+// address. After a switch lane 63 is at column -(kRollGroup - 1), inside the kRecPad pad records, so
+// every block writes; the sweep's first 48 steps, lane 63 at columns -63 .. -16, write into the end
+// of the pad beyond column C instead, which only garbage columns read.
+// Row sums: last rows complete in stacked-row order, which is time order (turn s, lane l reaches
+// column C at step s*P + l + C), so the next one comes from the entry table; the summing block
+// variant runs from that row's switch to its column C.
+// Early exit: the test of phmm_stack, on the same rows with the same sum, at the first block
+// boundary after lane 63's row has written column C (44 or 48 steps into the next turn). No lane of
+// the next turn has reached column C then (P > 63), so nothing of the dying testcase has been
+// stored: the rows in flight are abandoned and the sweep starts again at the next testcase's first
+// row, a va row, which ignores the records it is handed.
+constexpr int kRollGroup = 16;
+
+// wave steps of a stack (or an f64 work unit) of `rows` stacked rows over C columns with stripes of
+// `sh` rows: the rolled sweep where phmm_stack takes it, else a fill per stripe
+__host__ __device__ inline uint64_t stack_steps(int rows, int C, int sh, bool roll) {
+  const int turns = (rows + sh - 1) / sh;
+  if (roll && sh == kWave && C >= kWave && C <= kLdsHaplen && turns >= 2) {
+    const int P = (C + kRollGroup + 1 + 3) & ~3;
+    return (uint64_t)(turns - 1) * (uint64_t)P + (uint64_t)(C + rows - kWave * (turns - 1));
+  }
+  return (uint64_t)turns * (uint64_t)(C + sh);
+}
+
+template <typename T>
+__device__ __forceinline__ void setup_row(int rho, bool dead, int r, int R, const uint8_t *__restrict__ rbase,
+                                          const DevTab<T> &tab, T init_Y, T z_top, RowParams<T> &P,
+                                          LaneState<T> &st);
+
+// The rolled sweep of a stack's rows from `base` (at least two turns, C >= 64). Returns the stacked
+// row the stack goes on from: T_rows, or the next testcase's first row after an early exit.
+template <typename T, bool kExit>
+__device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, const int na, const int C, const int lane,
+                                           const int e_start, const int e_R, const uint32_t e_read,
+                                           const uint32_t e_out, const uint8_t *__restrict__ pool,
+                                           const DevTab<T> &tab, const T init_Y, Brec<T> *bnd, const uint8_t *hcol,
+                                           T *raw_out, unsigned long long *exit_stats) {
+  constexpr int G = kRollGroup, NG = kWave / G, U = 4;
+  static_assert(G % U == 0 && G <= kRecPad, "lane 63 writes from its switch on, at columns >= -(G - 1)");
+  const int Pd = (C + G + 1 + 3) & ~3;
+  const int nturn = (T_rows - base + kWave - 1) / kWave;
+  const int t_end = (nturn - 1) * Pd + C + (T_rows - base - kWave * (nturn - 1));
+  const bool last_lane = lane == kWave - 1;
+  struct L63 {
+    int r, R, start, out, may;
+  };
+  // turn s's constants and initial state of every lane (phmm_stack's per-stripe set-up; no lane starts
+  // at column 1, so none takes lane 0's special cases), and lane 63's row for the early exit
+  auto setup = [&](int s, RowParams<T> &Q, LaneState<T> &q, L63 &L) {
+    const int g = base + kWave * s + lane;
+    int lo = 0, hi = na - 1;
+    while (__builtin_amdgcn_ballot_w64(lo < hi)) {
+      const int mid = (lo + hi + 1) >> 1;
+      const int sm = __shfl(e_start, mid);
+      if (lo < hi) {
+        if (sm <= g) lo = mid; else hi = mid - 1;
+      }
+    }
+    const int start = __shfl(e_start, lo), R = __shfl(e_R, lo);
+    const uint32_t roff = (uint32_t)__shfl((int)e_read, lo);
+    const int r = g - start;
+    setup_row<T>(1, g >= T_rows, r, R, pool + roff, tab, init_Y, (T)0, Q, q);
+    if constexpr (kExit) {
+      L.r = __builtin_amdgcn_readlane(r, 63);
+      L.R = __builtin_amdgcn_readlane(R, 63);
+      L.start = __builtin_amdgcn_readlane(start, 63);
+      L.out = __builtin_amdgcn_readlane(__shfl((int)e_out, lo), 63);
+      L.may = __builtin_amdgcn_readlane((int)Q.rmask, 63) & kMayExit;
+    }
+  };
+  auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };  // wave-uniform, for the compiler
+  RowParams<T> P, Pn;
+  LaneState<T> st, sn;
+  L63 c63 = {0, 0, 0, 0, 0}, n63 = {0, 0, 0, 0, 0};
+  setup(0, P, st, c63);
+  setup(1, Pn, sn, n63);
+  T sumM = (T)0, sumX = (T)0;
+  const uint8_t *hl = hcol - lane;  // hl[t]: the code of the lane's column at step t
+  // pp[t]: lane 0's record in every lane but 63, which holds its own. Lane 63's first columns of the
+  // sweep, -63 .. -16, have no record: until step kFirst they go to the last records of the pad
+  // beyond column C, which are read as garbage columns only
+  constexpr int kFirst = kWave - kRecPad;
+  Brec<T> *pp = last_lane ? bnd + (C + kBndPad - kFirst) : bnd;
+  int first_t = kFirst;
+  int s3 = 0;         // the turn lane 63 is in
+  int sw = 0;         // next switch: group `sw` moves to turn s3 + 1 at step sw_t
+  int sw_t = Pd;      // (nturn >= 2)
+  int chk_s = 0;      // next turn whose lane-63 row is tested, at step chk_t
+  int chk_t = kExit ? (kWave + C + 3) & ~3 : INT_MAX;
+  // the next last row to complete: entry `ent`'s, in lane tg.lane at step tg.t, summed from step tg.from
+  // (its group's switch) and stored at tg.out; all wave-uniform
+  struct Target {
+    int t, from, lane;
+    uint32_t out;
+  };
+  auto target_of = [&](int en) -> Target {
+    const int ec = min(en, na - 1);
+    const int d = __builtin_amdgcn_readlane(e_start, ec) + __builtin_amdgcn_readlane(e_R, ec) + 1 - base;
+    const int s = d / kWave, l = d % kWave;
+    Target g;
+    g.lane = l;
+    g.t = uni(en < na ? s * Pd + l + C : INT_MAX);
+    g.from = uni(en < na ? (s ? s * Pd + (l / G) * G : 0) : INT_MAX);
+    g.out = (uint32_t)__builtin_amdgcn_readlane((int)e_out, ec);
+    return g;
+  };
+  int ent = uni((int)__builtin_ctzll(__builtin_amdgcn_ballot_w64(lane < na && e_start + e_R + 1 >= base) | (1ull << 63)));
+  Target tg = target_of(ent);
+  for (int t = 0; t < t_end;) {
+    if constexpr (kExit) {
+      if (t == chk_t) {
+        if (c63.r >= 2 && c63.r <= c63.R && c63.may) {
+          __syncthreads();
+          T acc = (T)0;
+#pragma unroll 1
+          for (int c = 1 + lane; c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
+          for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+          if (__builtin_amdgcn_readfirstlane(acc < (T)0.25e-28f ? 1 : 0)) {
+            const int next = c63.start + c63.R + 2;
+            if (lane == 0) {
+              raw_out[(uint32_t)c63.out] = (T)0;
+              atomicAdd(exit_stats, 1ull);
+              atomicAdd(exit_stats + 1,
+                        (unsigned long long)(next - (base + kWave * (chk_s + 1))) * (unsigned long long)C);
+            }
+            return next;
+          }
+        }
+        chk_s = uni(chk_s + 1);
+        chk_t = uni(chk_s + 1 < nturn ? chk_t + Pd : INT_MAX);
+      }
+    }
+    if (t == first_t) {
+      if (last_lane) pp = bnd - (kWave - 1);
+      first_t = INT_MAX;
+    }
+    if (t == sw_t) {
+      // group `sw` takes the next turn's constants and state (selects, so the block is straight-line)
+      const bool mine = lane / G == sw;
+      auto take = [mine](T &cur, T nxt) { cur = mine ? nxt : cur; };
+      take(P.pMY, Pn.pMY);
+      take(P.pYY, Pn.pYY);
+      take(P.dmatch, Pn.dmatch);
+      take(P.dmis, Pn.dmis);
+      take(P.nMM, Pn.nMM);
+      take(P.nGAPM, Pn.nGAPM);
+      take(P.nGAPMx, Pn.nGAPMx);
+      take(P.nMX, Pn.nMX);
+      take(P.nXX, Pn.nXX);
+      P.rmask = mine ? Pn.rmask : P.rmask;
+      take(st.Mp, (T)0);
+      take(st.wo, (T)0);
+      take(st.Yp, sn.Yp);
+      take(st.zo, sn.zo);
+      take(st.zd, sn.zd);
+      take(sumM, (T)0);
+      take(sumX, (T)0);
+      hl -= mine ? Pd : 0;
+      if (sw == 0) pp -= last_lane ? 0 : Pd;
+      if (sw == NG - 1) {
+        // lane 63 is at column -(G - 1) >= -kRecPad and goes on writing. The turn after this one is
+        // set up now (beyond the last turn: dead rows, never switched to)
+        s3 = uni(s3 + 1);
+        if (last_lane) pp = bnd - (kWave - 1) - s3 * Pd;
+        c63 = n63;
+        setup(s3 + 1, Pn, sn, n63);
+        sw = 0;
+        sw_t = uni(s3 + 1 < nturn ? (s3 + 1) * Pd : INT_MAX);
+      } else {
+        sw = uni(sw + 1);
+        sw_t = uni(sw_t + G);
+      }
+    }
+    // blocks of one variant up to the next event: a switch, the exit test, the block in which the
+    // next last row completes, the step its sums start at, or the sweep's last whole block
+    const bool sum = t >= tg.from;
+    int stop = min(min(min(chk_t, sw_t), first_t), min(t_end & ~(U - 1), tg.t & ~(U - 1)));
+    if (!sum) stop = min(stop, tg.from);
+    stop = uni(stop);
+    if (t < stop) {
+      auto run = [&](auto sum_tag) {
+        constexpr bool S = decltype(sum_tag)::value;
+        do {
+          Brec<T> *wp = pp + t;
+          const uint8_t *hp = hl + t;
+          const Brec<T> c0 = wp[0], c1 = wp[1], c2 = wp[2], c3 = wp[3];
+          const uint32_t h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3];
+          phmm_step<T, S, true>(c0, h0, st, P, sumM, sumX, wp, last_lane);
+          phmm_step<T, S, true>(c1, h1, st, P, sumM, sumX, wp + 1, last_lane);
+          phmm_step<T, S, true>(c2, h2, st, P, sumM, sumX, wp + 2, last_lane);
+          phmm_step<T, S, true>(c3, h3, st, P, sumM, sumX, wp + 3, last_lane);
+          t += U;
+        } while (t < stop);
+      };
+      if (sum) run(std::true_type{}); else run(std::false_type{});
+    } else {
+      // a last row reaches column C in this block (its sum is final at that step), or the sweep ends in it
+      const int n = min(U, t_end - t);
+      Brec<T> *wp = pp + t;
+      const uint8_t *hp = hl + t;
+#pragma unroll 1
+      for (int u = 0; u < n; u++) {
+        const Brec<T> c = wp[u];
+        const uint32_t h = hp[u];
+        phmm_step<T, true, true>(c, h, st, P, sumM, sumX, wp + u, last_lane);
+        if (t + u == tg.t) {
+          if (lane == tg.lane) raw_out[tg.out] = sumM + sumX;
+          ent = uni(ent + 1);
+          tg = target_of(ent);
+        }
+      }
+      t += n;
+    }
+  }
+  return T_rows;
+}
+
 // One stack. f32 pass: every testcase (kExit: with the early exit below); f64 pass: those whose f32
 // result is below MIN_ACCEPTED (all of them when `force`). Returns the number of testcases computed.
-template <typename T, bool kF64Pass, bool kExit = false>
+// kRoll && roll: the stack's runs of at least two turns over C >= 64 columns take phmm_rolled.
+template <typename T, bool kF64Pass, bool kExit = false, bool kRoll = false>
 __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__restrict__ stk_tc, const TcDesc *__restrict__ descs,
                           const uint8_t *__restrict__ pool, const DevTab<T> &tab, T *__restrict__ raw_out,
                           const float *__restrict__ raw_f, bool force, uint8_t *smem_raw, int part = 0,
-                          int parts = 1, unsigned long long *exit_stats = nullptr) {
+                          int parts = 1, unsigned long long *exit_stats = nullptr, bool roll = false) {
   const int lane = threadIdx.x;
   const int C = (int)S.C;
   // LDS: boundary records for columns [-kRecPad, C+kBndPad) and the haplotype codes for columns
@@ -459,6 +696,14 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
   // the stripe loop walks stacked rows from `base`; an early exit (f32 pass, `force` set) can skip the
   // rest of a testcase, so the stripes are not at fixed multiples of 64
   for (int base = 0; base < T_rows;) {
+    if constexpr (kRoll) {
+      if (roll && C >= kWave && T_rows - base > kWave) {
+        base = phmm_rolled<T, kExit && !kF64Pass>(base, T_rows, na, C, lane, e_start, e_R, e_read, e_out, pool, tab,
+                                                  init_Y, bnd, hcol, raw_out, exit_stats);
+        __syncthreads();
+        continue;
+      }
+    }
     const int g = base + lane;
     // the lane's testcase: the last entry starting at or before row g
     int lo = 0, hi = na - 1;
@@ -851,8 +1096,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8
 // `scratch` (scratch_stride bytes per workgroup, global memory: lane 63's record stores and lane 0's
 // loads of the next stripe are ordered by the stripe's __syncthreads), and both passes take the
 // stacks through a persistent grid (counter[2] f32, counter[3] f64).
+// The LDS kernels' registers are held to the waves per SIMD their LDS allows (f32 8, f64 4): with
+// phmm_rolled's second register set the compiler's own choice is 85-106 VGPRs for f32; held to 64, what
+// it spills is touched at the switches only, not in the 4-step blocks.
 template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false>
-__global__ __launch_bounds__(64) void phmm_forward(const Stack *__restrict__ stacks, int nstacks,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : (sizeof(T) == 4 ? 8 : 4), 8))) void phmm_forward(
+    const Stack *__restrict__ stacks, int nstacks,
                                                     const uint32_t *__restrict__ stk_tc,
                                                     const TcDesc *__restrict__ descs,
                                                     const uint8_t *__restrict__ pool, DevTab<T> tab,
@@ -861,6 +1110,7 @@ __global__ __launch_bounds__(64) void phmm_forward(const Stack *__restrict__ sta
                                                     size_t scratch_stride, const uint32_t *__restrict__ units) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   uint8_t *rec = kLong ? scratch + (size_t)blockIdx.x * scratch_stride : smem_raw;
+  const bool roll = (force >> 16) & 1;  // the LDS stacks' rolled sweep (phmm_rolled; GB_PHMM_ROLL)
   if constexpr (kF64Pass || kLong) {
     int done = 0;
     int *next = counter + (kLong ? (kF64Pass ? 3 : 2) : 1);
@@ -875,14 +1125,14 @@ __global__ __launch_bounds__(64) void phmm_forward(const Stack *__restrict__ sta
       k = __builtin_amdgcn_readfirstlane(__shfl(k, 0));
       if (k >= nwork) break;
       if (units) k = __builtin_amdgcn_readfirstlane((int)units[k]);
-      done += phmm_stack<T, kF64Pass>(stacks[k / parts], stk_tc, descs, pool, tab, raw_out, raw_f, (force & 0xFF) != 0,
-                                      rec, k % parts, parts);
+      done += phmm_stack<T, kF64Pass, false, !kLong>(stacks[k / parts], stk_tc, descs, pool, tab, raw_out, raw_f,
+                                                     (force & 0xFF) != 0, rec, k % parts, parts, nullptr, roll);
       __syncthreads();  // the next stack re-initialises the records
     }
     if (kF64Pass && threadIdx.x == 0 && done) atomicAdd(counter, done);
   } else {
-    phmm_stack<T, false, kExit>(stacks[blockIdx.x], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1,
-                                reinterpret_cast<unsigned long long *>(counter + 4));
+    phmm_stack<T, false, kExit, true>(stacks[blockIdx.x], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1,
+                                      reinterpret_cast<unsigned long long *>(counter + 4), roll);
   }
 }
 
@@ -895,8 +1145,8 @@ __global__ __launch_bounds__(64) void phmm_forward(const Stack *__restrict__ sta
 // depend on when it runs).
 __global__ __launch_bounds__(256) void f64_plan(const Stack *__restrict__ stacks, int nunits, int parts,
                                                 const uint32_t *__restrict__ stk_tc, const TcDesc *__restrict__ descs,
-                                                const float *__restrict__ raw_f, int force, uint8_t *__restrict__ ukey,
-                                                int *__restrict__ counter) {
+                                                const float *__restrict__ raw_f, int force, int roll,
+                                                uint8_t *__restrict__ ukey, int *__restrict__ counter) {
   __shared__ int hist[kPlanBuckets];
   for (int i = threadIdx.x; i < kPlanBuckets; i += blockDim.x) hist[i] = 0;
   __syncthreads();
@@ -911,7 +1161,7 @@ __global__ __launch_bounds__(256) void f64_plan(const Stack *__restrict__ stacks
     }
     int key = 0;
     if (rows) {
-      key = (((rows + kWave - 1) / kWave) * ((int)S.C + kWave) + 63) / 64;
+      key = (int)((stack_steps(rows, (int)S.C, kWave, roll != 0) + 63) / 64);
       key = key < 1 ? 1 : (key > kPlanBuckets - 1 ? kPlanBuckets - 1 : key);
       atomicAdd(&hist[key], 1);
     }
@@ -1107,6 +1357,7 @@ struct gb_phmm_batch {
   int f64_parts = 2;  // work units per stack in the f64 pass (GB_PHMM_F64_PARTS)
   bool f64_plan = true;  // the f64 pass's units by cost (f64_plan; GB_PHMM_F64_PLAN=0: stack order)
   bool f32_exit = true;  // the f32 pass's early exit (phmm_stack kExit; GB_PHMM_EXIT=0 turns it off)
+  bool roll = true;      // both passes' rolled sweep of the LDS stacks (phmm_rolled; GB_PHMM_ROLL=0: a fill per stripe)
   // host scratch of the fills (grow-only, host_reserve)
   std::vector<uint32_t> hid;
   std::vector<Stack> stacks;
@@ -1453,6 +1704,10 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   // finals, raw f64 and the fallback choice unchanged, a dropped testcase's raw f32 reads 0
   b->f32_exit = true;
   if (const char *e = getenv("GB_PHMM_EXIT")) b->f32_exit = atoi(e) != 0;
+  // rolled stripes (phmm_rolled) in both passes
+  b->roll = true;
+  if (const char *e = getenv("GB_PHMM_ROLL")) b->roll = atoi(e) != 0;
+  const bool roll = b->roll && b->rpl == 1;
   int stack_rows = kStackRows;
   if (total_rows / stack_rows < 4ll * 32 * b->cus) stack_rows = 1024;
   if (stack_rows == 1024 && total_rows / stack_rows < 16ll * b->cus) stack_rows = 512;
@@ -1484,12 +1739,13 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     } else {
       max_h_short = std::max(max_h_short, C);
     }
-    const uint64_t cost = std::min<uint64_t>((uint64_t)((rows + sh - 1) / sh) * (uint64_t)(C + sh), 0x7fffffffu);
+    const uint64_t cost = std::min<uint64_t>(stack_steps(rows, C, sh, false), 0x7fffffffu);
     key[ns_all] = ((uint64_t)is_long << 63) | ((0x7fffffffu - cost) << 32) | (uint32_t)ns_all;
     stacks[ns_all++] = S;
   }
   clk.mark("stack build");
-  {  // LSD radix sort of the keys' upper 32 bits, 8 bits a pass (the low 32 bits are the index)
+  // LSD radix sort of the keys' upper 32 bits, 8 bits a pass (the low 32 bits are the index)
+  auto sort_keys = [&](int ns_all) {
     uint32_t cnt[256];
     for (int shift = 32; shift < 64; shift += 8) {
       const uint64_t d0 = ns_all ? (key[0] >> shift) & 255 : 0;
@@ -1506,7 +1762,8 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
       for (int k = 0; k < ns_all; k++) key2[cnt[(key[k] >> shift) & 255]++] = key[k];
       std::swap(key, key2);
     }
-  }
+  };
+  sort_keys(ns_all);
   Stack *h_stacks = (Stack *)(b->h_stage + L.o_stk);
   for (int k = 0; k < ns_all; k++) h_stacks[k] = stacks[(uint32_t)key[k]];
   // Tail split: the stacks holding the last 10 % of the LPT order's cost are cut into stacks of at
@@ -1526,7 +1783,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     auto cost_of = [&](const Stack &S) -> uint64_t {
       int rows = 0;
       for (uint32_t t = 0; t < S.count; t++) rows += (int)(desc[order[S.first + t]].dims & 0xffff) + 2;
-      return (uint64_t)((rows + sh - 1) / sh) * (uint64_t)(S.C + sh);
+      return stack_steps(rows, (int)S.C, sh, false);
     };
     uint64_t total = 0;
     for (int k = 0; k < ns_short; k++) total += cost_of(h_stacks[k]);
@@ -1545,7 +1802,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
           P.count++;
           t++;
         }
-        pieces.push_back({(uint64_t)((rows + sh - 1) / sh) * (uint64_t)(S.C + sh), P});
+        pieces.push_back({stack_steps(rows, (int)S.C, sh, false), P});
       }
     }
     std::stable_sort(pieces.begin(), pieces.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
@@ -1554,6 +1811,22 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     for (const auto &pc : pieces) h_stacks[k++] = pc.second;
     for (const auto &ls : longs) h_stacks[k++] = ls;
     ns_all = k;
+  }
+  // Which testcases share a stack is decided above by the fill-per-stripe cost, whatever the sweep (a
+  // dropped testcase's raw f32 depends on where the early exit's stripes fall in its stack). The launch
+  // order of the LDS stacks is by the cost of the sweep they take: the rolled one's wave steps.
+  if (roll) {
+    const int ns_short = ns_all - n_long;
+    for (int k = 0; k < ns_short; k++) {
+      const Stack &S = h_stacks[k];
+      int rows = 0;
+      for (uint32_t t = 0; t < S.count; t++) rows += (int)(desc[order[S.first + t]].dims & 0xffff) + 2;
+      const uint64_t cost = std::min<uint64_t>(stack_steps(rows, (int)S.C, sh, true), 0x7fffffffu);
+      key[k] = ((0x7fffffffu - cost) << 32) | (uint32_t)k;
+      stacks[k] = S;
+    }
+    sort_keys(ns_short);
+    for (int k = 0; k < ns_short; k++) h_stacks[k] = stacks[(uint32_t)key[k]];
   }
   clk.mark("stacks");
   if (int st = batch_reserve(b, n, pool_bytes)) return st;
@@ -1798,7 +2071,7 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
       } else if (ns > 0) {
         hipLaunchKernelGGL(f32k, dim3(ns), dim3(kWave), lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                            b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr,
-                           b->d_count, 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr);
+                           b->d_count, b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr);
       }
       if (nl > 0)
         hipLaunchKernelGGL((phmm_forward<float, false, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
@@ -1815,13 +2088,14 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
       if (b->f64_plan) {
         const dim3 pg((unsigned)((nunits + 255) / 256)), pb(256);
         hipLaunchKernelGGL(f64_plan, pg, pb, 0, b->stream, b->d_stacks, nunits, b->f64_parts, b->d_stk_tc, b->d_desc,
-                           (const float *)b->d_rf, b->force_f64 ? 1 : 0, b->d_ukey, b->d_count);
+                           (const float *)b->d_rf, b->force_f64 ? 1 : 0, b->roll ? 1 : 0, b->d_ukey, b->d_count);
         hipLaunchKernelGGL(f64_plan_order, pg, pb, 0, b->stream, nunits, (const uint8_t *)b->d_ukey, b->d_count,
                            b->d_units);
       }
       hipLaunchKernelGGL(f64k, dim3(g64), dim3(kWave), lds_d, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                          b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd, (const float *)b->d_rf,
-                         b->d_count, (b->force_f64 ? 1 : 0) | (b->f64_parts << 8), (uint8_t *)nullptr, (size_t)0,
+                         b->d_count, (b->force_f64 ? 1 : 0) | (b->f64_parts << 8) | (b->roll ? 1 << 16 : 0),
+                         (uint8_t *)nullptr, (size_t)0,
                          b->f64_plan ? (const uint32_t *)b->d_units : nullptr);
     }
     if (nl > 0)
