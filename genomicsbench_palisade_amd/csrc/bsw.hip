@@ -319,7 +319,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NCH >= 16 ? 
   const int o_ins = SYM ? o_del : A.o_ins, e_ins = SYM ? e_del : A.e_ins;
   const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
   const uint8_t *qry = A.qry + P.q_off;
-  const uint8_t *tgt = A.tgt + P.t_off;
+  // a lane without target bases (an empty target, which may lie at the very end of the sequence
+  // buffer, or a lane past the launch's last pair) has no byte of its own to read: its row-ahead loads
+  // below are aimed at the pair table, which holds at least one entry, and their value is never used
+  const uint8_t *tgt = tlen > 0 ? A.tgt + P.t_off : reinterpret_cast<const uint8_t *>(A.pairs);
 
   // query codes, 4 bits per column, 8 columns per word, staged in LDS (Qs[c][lane]) so they cost
   // no VGPRs; eh row 0 (bandedSWA.cpp:157-159) computed in registers
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NCH >= 16 ? 
   // a row of sweeping hides its latency, and the 256-VGPR variants keep it out of scratch (a
   // four-row prefetch group spilled there and waited on each load)
   const int tmax = max(tlen - 1, 0);
-  uint32_t tnext = tgt[0];
+  uint32_t tnext = tlen > 0 ? tgt[0] : 4u;
   // per-lane constants used once per row (target pointer, last row, band width) live in LDS and are
   // re-read each row: in the 256-VGPR variants they were spilled to scratch instead, and a scratch
   // reload's vmcnt wait also waited for the row-ahead target load
