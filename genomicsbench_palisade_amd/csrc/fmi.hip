@@ -935,6 +935,8 @@ static_assert(kCap >= 16, "the first 16 entries of a slot are loaded uncondition
 
 __global__ __launch_bounds__(256) void sort_slots(gb_smem *__restrict__ slots, gb_smem *__restrict__ big,
                                                   const int32_t *__restrict__ ovf_pos,
+                                                  const int32_t *__restrict__ ovf_list,
+                                                  const int32_t *__restrict__ ovf_n,
                                                   const int32_t *__restrict__ counts, int32_t nreads) {
   const int lane = threadIdx.x & 63, g = lane >> 4, sl = lane & 15;
   const int nwaves = gridDim.x * (blockDim.x >> 6);
@@ -969,7 +971,15 @@ __global__ __launch_bounds__(256) void sort_slots(gb_smem *__restrict__ slots, g
         }
         if (lane < nw) sw[rk] = ew;
       } else if (lane == 0) {
-        heap_sort(big + (size_t)ovf_pos[rw] * kBigCap, min(nw, kBigCap));
+        // A read above kCap that found the pool exhausted holds no big slot: mark_overflow wrote no
+        // ovf_pos entry for it, and what the entry holds (never initialised, or a position from an
+        // earlier search on these buffers) is not the read's. Only a position below this search's
+        // slot count whose owner is this read is one (every ovf_list entry below the count is
+        // written by this search); any other read has nothing to sort here, `fatal` is set and the
+        // host reports it before any result is read.
+        const int pos = ovf_pos[rw];
+        if ((unsigned)pos < (unsigned)min(*ovf_n, kMaxOvf) && ovf_list[pos] == rw)
+          heap_sort(big + (size_t)pos * kBigCap, min(nw, kBigCap));
       }
     }
   }
@@ -1561,7 +1571,7 @@ int gb_fmi_search(gb_fmi_reads *R, int32_t min_seed_len) {
     GB_HIP(hipGetLastError());
     const int sort_blocks = std::max(1, std::min(256 * 8, (R->nreads + 15) / 16));  // 4 waves x 4 reads
     hipLaunchKernelGGL(gbfmi::sort_slots, dim3(sort_blocks), dim3(256), 0, R->stream, R->d_slots, R->d_big,
-                       R->d_ovf_pos, R->d_counts, R->nreads);
+                       R->d_ovf_pos, R->d_ovf_list, R->d_ctl + 1, R->d_counts, R->nreads);
     GB_HIP(hipGetLastError());
   }
   GB_HIP(hipEventRecord(R->ev[1], R->stream));

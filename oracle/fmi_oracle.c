@@ -472,7 +472,10 @@ static int compare_smem(const void *a, const void *b) {
  * batch_size. enc_qdb has stride max_readlength (fmi.cpp:141-177); lens[r] = read length.
  * out must hold numReads * (2*max_readlength + 8) SMEMs (returns -1 when it would overflow);
  * batch_counts[b] = numTotalSmem of batch b; phase_counts[3] += num_smem1/2/3.
+ * The reseeding task arrays hold batch_size * 64 entries, the reference's allocation
+ * (fmi.cpp:246-248); a batch with more phase-2 tasks returns FMI_ORACLE_ERR_TASKS (-2).
  * Returns the total number of SMEMs (totalSmems, fmi.cpp:381). */
+#define FMI_ORACLE_ERR_TASKS (-2)
 int64_t fmi_oracle_run(or_fmi *f, const uint8_t *enc_qdb, const int32_t *lens, int32_t numReads,
                        int32_t max_readlength, int32_t batch_size, int32_t minSeedLen, or_smem *out,
                        int64_t out_cap, int64_t *batch_counts, int64_t *phase_counts) {
@@ -500,15 +503,21 @@ int64_t fmi_oracle_run(or_fmi *f, const uint8_t *enc_qdb, const int32_t *lens, i
     int64_t n1 = 0, n2 = 0, n3 = 0;
     smems_all_pos(f, q, min_intv, rid, bc, bl, cum, minSeedLen, tmp, &n1, prev);
     int64_t pos = 0;
+    const int64_t task_cap = (int64_t)batch_size * 64;  /* rid / qpos / min_intv, as the reference sizes them */
     for (int64_t j = 0; j < n1; j++) {
       or_smem *p = &tmp[j];
       int start = (int)p->m, end = (int)p->n + 1;
       if (end - start < split_len || p->s > splitWidth) continue;
+      if (pos >= task_cap) {  /* more reseeding tasks than the arrays hold: refuse, do not overrun */
+        total = FMI_ORACLE_ERR_TASKS;
+        break;
+      }
       rid[pos] = (int32_t)p->rid;
       qpos[pos] = (int16_t)((end + start) >> 1);
       min_intv[pos] = (int32_t)(p->s + 1);
       pos++;
     }
+    if (total < 0) break;
     smems_one_pos(f, q, qpos, min_intv, rid, (int32_t)pos, bl, cum, minSeedLen, tmp + n1, &n2, prev);
     for (int32_t j = 0; j < bc; j++) min_intv[j] = maxMemIntv;
     n3 = seed_strategy(f, q, min_intv, bc, bl, cum, minSeedLen + 1, tmp + n1 + n2);

@@ -85,7 +85,9 @@ class OracleIndex:
         tot = self.lib.fmi_oracle_run(self.h, codes.ctypes.data, lens.ctypes.data, nreads, maxlen,
                                       batch_size, min_seed_len, out.ctypes.data, cap,
                                       bc.ctypes.data, pc.ctypes.data)
-        assert tot >= 0
+        assert tot != -2, (f"fmi oracle: a batch of {batch_size} reads has more reseeding (phase-2) tasks than its "
+                           f"task arrays hold ({batch_size * 64}, the reference's allocation): use a larger batch_size")
+        assert tot >= 0, f"fmi oracle: output capacity {cap} exceeded"
         return out[:tot], bc, pc
 
     def run_threaded(self, codes, lens, threads, batch_size=512, min_seed_len=19, collect=False):

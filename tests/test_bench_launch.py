@@ -51,7 +51,8 @@ def test_launch_forwards_rank0_stdout_only_and_propagates_failure(tmp_path, capf
     child.write_text(
         "import os, sys\n"
         "r = int(os.environ['RANK'])\n"
-        "print('line from rank', r, os.environ['WORLD_SIZE'], os.environ['MASTER_ADDR'], flush=True)\n"
+        # one write per line: the ranks share a stream, and an unbuffered print writes word by word
+        "os.write(1, ('line from rank %d %s %s\\n' % (r, os.environ['WORLD_SIZE'], os.environ['MASTER_ADDR'])).encode())\n"
         "sys.exit(int(os.environ.get('FAIL_RANK', '-1')) == r and 3 or 0)\n")
     assert bench.launch(3, [], cmd=[sys.executable, str(child)], poll_s=0.05) == 0
     out, err = capfd.readouterr()

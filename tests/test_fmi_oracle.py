@@ -49,6 +49,21 @@ def test_oracle_batch_order_and_counts(golden):
     oi.close()
 
 
+def test_oracle_refuses_more_reseed_tasks_than_its_arrays_hold():
+    """The reseeding task arrays hold batch_size * 64 entries (the reference's allocation): random
+    128-base reads against a 4 000-base reference at min_seed_len 2 give more phase-2 tasks per
+    512-read batch than that, which the oracle refuses with its own code instead of overrunning them;
+    the same reads in batches with room for them run."""
+    oi = fmi_util.OracleIndex(gen.fmi_reference(4000, seed=3, repeat_frac=0.0))
+    codes = np.random.default_rng(1).integers(0, 4, (512, 128), dtype=np.uint8)
+    lens = np.full(512, 128, np.int32)
+    with pytest.raises(AssertionError, match="more reseeding .* tasks than its task arrays hold"):
+        oi.run(codes, lens, batch_size=512, min_seed_len=2)
+    sm, bc, pc = oi.run(codes[:64], lens[:64], batch_size=64, min_seed_len=6)
+    assert len(sm) == bc.sum() == pc.sum() > 0
+    oi.close()
+
+
 def test_index_file_roundtrip(tmp_path, golden):
     p = str(tmp_path / "g.bwt.2bit.64")
     a = fmi_util.OracleIndex(golden["ref"][:50000], path_out=p)
