@@ -235,6 +235,16 @@ __device__ __forceinline__ double select_dist(uint32_t rmask, uint32_t h, double
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
+// A lane's haplotype code of one column. The empty asm keeps the zero extension in the load's basic
+// block, where the byte load gives it for free; left to the optimiser it sinks to the step that uses
+// the code, behind lane 63's record write, and the code crosses the blocks as a byte that is masked
+// again there (a v_and_b32 0xff per code, 3 of the 70 VALU instructions of a 4-step f32 block).
+__device__ __forceinline__ uint32_t load_code(const uint8_t *p) {
+  uint32_t h = *p;
+  asm volatile("" : "+v"(h));
+  return h;
+}
+
 // Per-lane constants of one stripe (initializeVectors, avx-pairhmm-template.h:83-128): the lane's
 // own row (Y recurrence, emission) and the NEXT row's transitions (the partials z/w it hands down).
 // nGAPMx is nGAPM for the X term of the bracket; a separate register so that the virtual row 0 of
@@ -311,7 +321,7 @@ __device__ __forceinline__ void phmm_stripe(int steps, LaneState<T> &st, const R
   int target = (kSum && pend) ? C + __builtin_ctzll(pend) - 1 : INT_MAX;
   auto single = [&](int tt, auto wr_tag) {
     constexpr bool W = decltype(wr_tag)::value;
-    phmm_step<T, kSum, W>(bnd[tt + 1], hl[tt], st, P, sumM, sumX, bnd + (tt - (kWave - 2)), last_lane);
+    phmm_step<T, kSum, W>(bnd[tt + 1], load_code(hl + tt), st, P, sumM, sumX, bnd + (tt - (kWave - 2)), last_lane);
     if (kSum && tt == target) {
       if (lane == __builtin_ctzll(pend)) *out = sumM + sumX;
       pend &= pend - 1;
@@ -334,7 +344,8 @@ __device__ __forceinline__ void phmm_stripe(int steps, LaneState<T> &st, const R
       // covered by the other waves on the SIMD
       Brec<T> *wr = wb + t;
       const Brec<T> c0 = wr[kWave - 1], c1 = wr[kWave], c2 = wr[kWave + 1], c3 = wr[kWave + 2];
-      const uint32_t h0 = hl[t], h1 = hl[t + 1], h2 = hl[t + 2], h3 = hl[t + 3];
+      const uint32_t h0 = load_code(hl + t), h1 = load_code(hl + t + 1);
+      const uint32_t h2 = load_code(hl + t + 2), h3 = load_code(hl + t + 3);
       phmm_step<T, kSum, W>(c0, h0, st, P, sumM, sumX, wr, last_lane);
       phmm_step<T, kSum, W>(c1, h1, st, P, sumM, sumX, wr + 1, last_lane);
       phmm_step<T, kSum, W>(c2, h2, st, P, sumM, sumX, wr + 2, last_lane);
@@ -608,7 +619,7 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
           Brec<T> *wp = pp + t;
           const uint8_t *hp = hl + t;
           const Brec<T> c0 = wp[0], c1 = wp[1], c2 = wp[2], c3 = wp[3];
-          const uint32_t h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3];
+          const uint32_t h0 = load_code(hp), h1 = load_code(hp + 1), h2 = load_code(hp + 2), h3 = load_code(hp + 3);
           phmm_step<T, S, true>(c0, h0, st, P, sumM, sumX, wp, last_lane);
           phmm_step<T, S, true>(c1, h1, st, P, sumM, sumX, wp + 1, last_lane);
           phmm_step<T, S, true>(c2, h2, st, P, sumM, sumX, wp + 2, last_lane);
@@ -625,7 +636,7 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
 #pragma unroll 1
       for (int u = 0; u < n; u++) {
         const Brec<T> c = wp[u];
-        const uint32_t h = hp[u];
+        const uint32_t h = load_code(hp + u);
         phmm_step<T, true, true>(c, h, st, P, sumM, sumX, wp + u, last_lane);
         if (t + u == tg.t) {
           if (lane == tg.lane) raw_out[tg.out] = sumM + sumX;
