@@ -17,7 +17,7 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize
+.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -104,6 +104,18 @@ tests/_build/regs_host_check: tests/cpp/regs_host_check.cpp $(REGS_CHECK_SRCS) $
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(REGS_CHECK_SRCS) \
+	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the same for the host bookkeeping of gb_bsw_mate_rescue: the rounds run over alignment results that the
+# program supplies from a table, so no device is touched. Not part of `all`.
+MATESW_CHECK_SRCS := $(CSRC)/bsw_matesw.hip $(CSRC)/bsw_local.hip $(CSRC)/bsw_gencigar.hip $(CSRC)/bsw_global.hip \
+                     $(CSRC)/gb_common.cpp
+matesw-sanitize: tests/_build/matesw_host_check
+	tests/_build/matesw_host_check
+tests/_build/matesw_host_check: tests/cpp/matesw_host_check.cpp $(MATESW_CHECK_SRCS) $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(MATESW_CHECK_SRCS) \
 	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:

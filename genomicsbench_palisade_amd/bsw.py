@@ -781,3 +781,120 @@ def finish_regs_timing():
     check(_decl_regs().gb_bsw_finish_regs_timing(*[ctypes.byref(x) for x in t], ctypes.byref(r), ctypes.byref(q),
                                                 ctypes.byref(h)), "gb_bsw_finish_regs_timing")
     return t[0].value, t[1].value, t[2].value, r.value, q.value, h.value
+
+
+# ---- mate rescue (mem_pestat, and mem_sam_pe's rescue loop around mem_matesw; bwamem_pair.c:23-180, 265-276) ----
+
+# struct gb_bsw_pestat (include/gb_bsw.h): mem_pestat_t
+PESTAT_DTYPE = np.dtype([("low", "<i4"), ("high", "<i4"), ("failed", "<i4"), ("_pad", "<i4"), ("avg", "<f8"),
+                         ("std", "<f8")])
+assert PESTAT_DTYPE.itemsize == 32
+PESTAT_FIELDS = ("low", "high", "failed", "avg", "std")
+
+
+class PeOpt(ctypes.Structure):
+    """gb_bsw_pe_opt: the mem_opt_t fields mem_pestat and mem_matesw read."""
+    _fields_ = ([(k, ctypes.c_int32) for k in "a b o_del e_del o_ins e_ins min_seed_len max_chain_gap pen_unpaired "
+                                              "max_matesw max_ins".split()]
+                + [(k, ctypes.c_float) for k in "mask_level mask_level_redun".split()])
+
+
+_PE_OPT_FLOATS = ("mask_level", "mask_level_redun")
+
+
+def _decl_matesw():
+    L = _decl_regs()
+    if getattr(L, "_bsw_matesw_decl", False):
+        return L
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    L.gb_bsw_pe_default_opt.argtypes = [vp]
+    L.gb_bsw_pe_default_opt.restype = None
+    L.gb_bsw_pestat.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.gb_bsw_mate_rescue.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.gb_bsw_mate_rescue_timing.argtypes = [vp] * 6
+    L._bsw_matesw_decl = True
+    return L
+
+
+def pe_opt(**kw):
+    """bwa's defaults (bwamem.c:50-86): a 1, b 4, gaps 6 / 1, min_seed_len 19, max_chain_gap 10000, pen_unpaired 17,
+    max_matesw 50, max_ins 10000, mask_level 0.5, mask_level_redun 0.95; keywords override."""
+    o = PeOpt()
+    _decl_matesw().gb_bsw_pe_default_opt(ctypes.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, float(v) if k in _PE_OPT_FLOATS else int(v))
+    return o
+
+
+def pestat_raw(l_pac, reg_off, regs, opt=None, pes=None):
+    """gb_bsw_pestat without the status check: (status, pes); pes (a PESTAT_DTYPE array of 4) is written only by
+    a call that succeeds."""
+    opt = opt if opt is not None else pe_opt()
+    reg_off = np.ascontiguousarray(reg_off, np.int64)
+    regs = np.ascontiguousarray(regs, ALNREG_DTYPE)
+    pes = np.zeros(4, PESTAT_DTYPE) if pes is None else pes
+    st = _decl_matesw().gb_bsw_pestat(ctypes.byref(opt), int(l_pac), len(reg_off) - 1, _buf(reg_off), _buf(regs),
+                                      pes.ctypes.data)
+    return st, pes
+
+
+def pestat(l_pac, reg_off, regs, opt=None):
+    """gb_bsw_pestat: mem_pestat over the stage-0 regions of an even number of reads (reads 2p and 2p + 1 are
+    pair p). Returns a PESTAT_DTYPE array of 4, one record per orientation FF, FR, RF, RR. Runs on the host."""
+    st, pes = pestat_raw(l_pac, reg_off, regs, opt)
+    check(st, "gb_bsw_pestat")
+    return pes
+
+
+def mate_rescue_raw(ref, pes, qbuf, idq, l_query, reg_off, regs, opt=None, params=None, contig_end=None,
+                    n_contigs=None, out_cap=None, want_n_sw=True):
+    """gb_bsw_mate_rescue without the status check: a dict with status, regs (out_cap records, zero where the
+    call wrote nothing), out_off, n_out, n_sw, out_used. out_cap defaults to the bound that always suffices."""
+    opt = opt if opt is not None else pe_opt()
+    params = params if params is not None else default_params()
+    pes = np.ascontiguousarray(pes, PESTAT_DTYPE)
+    qbuf = np.ascontiguousarray(qbuf, np.uint8)
+    idq = np.ascontiguousarray(idq, np.int64)
+    l_query = np.ascontiguousarray(l_query, np.int32)
+    reg_off = np.ascontiguousarray(reg_off, np.int64)
+    regs = np.ascontiguousarray(regs, ALNREG_DTYPE)
+    n = len(idq)
+    assert n % 2 == 0 and len(pes) == 4
+    ce = None if contig_end is None else np.ascontiguousarray(contig_end, np.int64)
+    nc = (len(ce) if ce is not None else 1) if n_contigs is None else int(n_contigs)
+    if out_cap is None:
+        n_reg = np.diff(reg_off)  # every region of the mate can be an anchor, each adds at most four
+        out_cap = int(n_reg.sum() + 4 * np.minimum(n_reg, max(int(opt.max_matesw), 0)).sum()) if n else 0
+    out = np.zeros(max(int(out_cap), 1), ALNREG_DTYPE)
+    out_off = np.full(max(n, 1), -1, np.int64)
+    n_out = np.full(max(n, 1), -1, np.int32)
+    n_sw = np.full(max(n // 2, 1), -1, np.int32)
+    used = ctypes.c_int64(-1)
+    st = _decl_matesw().gb_bsw_mate_rescue(
+        ctypes.byref(params), ctypes.byref(opt), pes.ctypes.data, ref.h, None if ce is None else ce.ctypes.data, nc,
+        _buf(qbuf), len(qbuf), n // 2, _buf(idq), _buf(l_query), _buf(reg_off), _buf(regs), out.ctypes.data,
+        int(out_cap), out_off.ctypes.data, n_out.ctypes.data, n_sw.ctypes.data if want_n_sw else None,
+        ctypes.byref(used))
+    return dict(status=st, regs=out[:int(out_cap)], out_off=out_off[:n], n_out=n_out[:n], n_sw=n_sw[:n // 2],
+                out_used=used.value)
+
+
+def mate_rescue(ref, pes, qbuf, idq, l_query, reg_off, regs, **kw):
+    """gb_bsw_mate_rescue: the rescue loop of mem_sam_pe around mem_matesw for pairs of reads (2p, 2p + 1). regs
+    (never written) holds the reads' stage-0 regions, reg_off one entry per read plus one, pes is pestat()'s
+    result. Keywords: opt (pe_opt()), params (mat), contig_end, n_contigs, out_cap. Returns a dict: read r's
+    final list is regs[out_off[r]:out_off[r] + n_out[r]]; n_sw[p] counts the alignments pair p performed."""
+    res = mate_rescue_raw(ref, pes, qbuf, idq, l_query, reg_off, regs, **kw)
+    check(res["status"], "gb_bsw_mate_rescue")
+    return res
+
+
+def mate_rescue_timing():
+    """(fetch_ms, dp_ms, region_ms, host_ms, rounds, requests) of this thread's last mate_rescue: the device time
+    of the window and fetch kernels, of the local DP and of the region kernel, the host time of the bookkeeping
+    between the rounds, the rounds that had a request, and the requests."""
+    t = [ctypes.c_float() for _ in range(4)]
+    r, q = ctypes.c_int32(0), ctypes.c_int64(0)
+    check(_decl_matesw().gb_bsw_mate_rescue_timing(*[ctypes.byref(x) for x in t], ctypes.byref(r), ctypes.byref(q)),
+          "gb_bsw_mate_rescue_timing")
+    return t[0].value, t[1].value, t[2].value, t[3].value, r.value, q.value

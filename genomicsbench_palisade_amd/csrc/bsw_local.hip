@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "../../include/gb_bsw.h"
+#include "bsw_local_internal.h"
 #include "gb_common.h"
 
 static_assert(sizeof(gb_bsw_lpair) == 56, "gb_bsw_lpair is 56 bytes (include/gb_bsw.h)");
@@ -64,11 +65,6 @@ constexpr uint32_t kRowMask = (1u << kRowBits) - 1u;
 constexpr int kStripeBias = 1 << 24;  // above the spread of F's scan terms (< 2^15 + 2^23 + 2^15), times p <= 16 below 2^30
 constexpr int kFlags = GB_KSW_XBYTE | GB_KSW_XSTOP | GB_KSW_XSUBO | GB_KSW_XSTART;
 
-struct Pair {  // device descriptor, 32 B
-  int64_t t_off, q_off;
-  int32_t tlen, qlen, xtra, pad;
-};
-
 struct Args {
   const Pair *pairs;
   int64_t n;
@@ -80,9 +76,6 @@ struct Args {
   int oe_del, e_del, oe_ins, e_ins, max_mat;
   int8_t mat[28];
 };
-
-// entries a pass over tlen rows can append: never on two adjacent rows (ksw.c:193)
-__host__ __device__ inline int64_t list_entries(int tlen) { return (tlen + 1) / 2 + 1; }
 
 // wave-wide inclusive max scan (Hillis-Steele in 16-lane rows, then row broadcasts)
 __device__ __forceinline__ int scan_max(int v) {
@@ -308,20 +301,6 @@ int64_t chunk_pairs() {  // GB_BSW_LOCAL_CHUNK (tests: many chunks from a small 
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kChunkPairs)) : kChunkPairs;
 }
 
-struct Ws {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
-  int device = -1, num_cus = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  gb::DevBuf<uint8_t> d_tgt, d_qry;
-  gb::DevBuf<Pair> d_pairs;
-  gb::DevBuf<int32_t> d_out8;
-  gb::DevBuf<uint32_t> d_list;
-  gb::DevBuf<unsigned int> d_ctl;  // [0] work counter
-  gb::PinnedBuf<Pair> h_pairs;
-  gb::PinnedBuf<int32_t> h_out8;
-  float kernel_ms = 0.f;
-};
-
 thread_local std::vector<Ws *> g_ws;
 
 Ws *find_ws(int dev) {
@@ -352,6 +331,39 @@ int get_ws(int dev, Ws **out) {
   }
   g_ws.push_back(W);
   *out = W;
+  return GB_OK;
+}
+
+int run_resident(Ws *W, const gb_bsw_params *params, int max_mat, const Pair *d_pairs, int64_t m, const uint8_t *d_tgt,
+                 const uint8_t *d_qry, int32_t *d_out8, int64_t list_cap, hipEvent_t e0, hipEvent_t e1) {
+  int st;
+  const int64_t blocks = std::max<int64_t>(
+      1, std::min<int64_t>((int64_t)W->num_cus * kBlocksPerCU, (m + kWavesPerBlock - 1) / kWavesPerBlock));
+  if ((st = W->d_list.reserve((size_t)(blocks * kWavesPerBlock * list_cap)))) return st;
+  GB_HIP(hipMemsetAsync(W->d_ctl, 0, 4 * sizeof(unsigned int), W->stream));
+  Args A;
+  A.pairs = d_pairs;
+  A.n = m;
+  A.tgt = d_tgt;
+  A.qry = d_qry;
+  A.out8 = d_out8;
+  A.list = W->d_list;
+  A.list_cap = list_cap;
+  A.next = W->d_ctl;
+  A.oe_del = params->o_del + params->e_del;
+  A.e_del = params->e_del;
+  A.oe_ins = params->o_ins + params->e_ins;
+  A.e_ins = params->e_ins;
+  A.max_mat = max_mat;
+  std::memset(A.mat, 0, sizeof(A.mat));
+  std::memcpy(A.mat, params->mat, 25);
+  if (e0) GB_HIP(hipEventRecord(e0, W->stream));
+  if (params->o_ins == 0)
+    hipLaunchKernelGGL(bsw_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, W->stream, A);
+  else
+    hipLaunchKernelGGL(bsw_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, W->stream, A);
+  GB_HIP(hipGetLastError());
+  if (e1) GB_HIP(hipEventRecord(e1, W->stream));
   return GB_OK;
 }
 
@@ -449,35 +461,9 @@ int gb_bsw_local(const gb_bsw_params *params, gb_bsw_lpair *pairs, int64_t n, co
       hp[k] = Pair{s.idr, s.idq, s.len1, s.len2, s.xtra, 0};
       if (s.xtra & GB_KSW_XSUBO) list_cap = std::max(list_cap, list_entries(s.len1));
     }
-    const int64_t blocks = std::max<int64_t>(
-        1, std::min<int64_t>((int64_t)W->num_cus * kBlocksPerCU, (m + kWavesPerBlock - 1) / kWavesPerBlock));
-    if ((st = W->d_list.reserve((size_t)(blocks * kWavesPerBlock * list_cap)))) return st;
-    const unsigned int ctl0[4] = {0u, 0u, 0u, 0u};
-    GB_HIP(hipMemcpyAsync(W->d_ctl, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, W->stream));
     GB_HIP(hipMemcpyAsync(W->d_pairs, hp, (size_t)m * sizeof(Pair), hipMemcpyHostToDevice, W->stream));
-    Args A;
-    A.pairs = W->d_pairs;
-    A.n = m;
-    A.tgt = W->d_tgt;
-    A.qry = W->d_qry;
-    A.out8 = W->d_out8;
-    A.list = W->d_list;
-    A.list_cap = list_cap;
-    A.next = W->d_ctl;
-    A.oe_del = params->o_del + params->e_del;
-    A.e_del = params->e_del;
-    A.oe_ins = params->o_ins + params->e_ins;
-    A.e_ins = params->e_ins;
-    A.max_mat = max_mat;
-    std::memset(A.mat, 0, sizeof(A.mat));
-    std::memcpy(A.mat, params->mat, 25);
-    GB_HIP(hipEventRecord(W->ev[0], W->stream));
-    if (params->o_ins == 0)
-      hipLaunchKernelGGL(bsw_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, W->stream, A);
-    else
-      hipLaunchKernelGGL(bsw_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, W->stream, A);
-    GB_HIP(hipGetLastError());
-    GB_HIP(hipEventRecord(W->ev[1], W->stream));
+    if ((st = run_resident(W, params, max_mat, W->d_pairs, m, W->d_tgt, W->d_qry, W->d_out8, list_cap, W->ev[0], W->ev[1])))
+      return st;
     int32_t *ho = W->h_out8;
     GB_HIP(hipMemcpyAsync(ho, W->d_out8, (size_t)m * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, W->stream));
     GB_HIP(hipStreamSynchronize(W->stream));

@@ -42,6 +42,10 @@
 // (100, 10000, 500, 19, 0, 2^30, 0.5, 0.5). One line per chain goes to the -o file or to stdout as for
 // -global: read pos rid is_alt weight kept n_seeds (tab separated), then per seed, in mem_print_chain's
 // field order, score;len;qbeg,rbeg. -mkchains excludes the other modes and needs no -pac.
+// -materescue -pac <file.pac> <file> runs mate rescue (gb_bsw_mate_rescue) over -finishregs' records, reads 2p and
+// 2p + 1 being pair p, behind a first line "pes low high failed" times four (FF, FR, RF, RR) or "pes auto"
+// (gb_bsw_pestat over the file's regions); -unpaired, -maxmatesw and -maxins give pen_unpaired, max_matesw and
+// max_ins (17, 50, 10000), -contigs the contigs' ends. It prints -finishregs' columns for every read's final list.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -400,6 +404,53 @@ struct RegsOpt {
   float redun = 0.95f;
 };
 
+struct RegionFile {  // -finishregs' and -materescue's input
+  std::vector<uint8_t> qer;
+  std::vector<int64_t> idq, reg_off = std::vector<int64_t>(1, 0);
+  std::vector<int32_t> lq;
+  std::vector<gb_bsw_alnreg> regs;
+  int max_rid = 0;
+};
+
+// per read "bases n_regions", then per region thirteen numbers; 0 on success
+static int read_regions(FILE *f, RegionFile &R) {
+  std::vector<uint8_t> &qer = R.qer;
+  std::vector<int64_t> &idq = R.idq, &reg_off = R.reg_off;
+  std::vector<int32_t> &lq = R.lq;
+  std::vector<gb_bsw_alnreg> &regs = R.regs;
+  int &max_rid = R.max_rid;
+  std::vector<char> line(1 << 12);
+  while (fgets(line.data(), (int)line.size(), f)) {
+    if (line[0] == '\n' || line[0] == '\r') continue;
+    size_t n = 0;
+    while (line[n] >= '0' && line[n] <= '4') ++n;
+    long nr = -1;
+    if (n < 1 || sscanf(line.data() + n, "%ld", &nr) != 1 || nr < 0) {
+      fprintf(stderr, "read %zu: expected \"bases n_regions\"\n", lq.size());
+      return 1;
+    }
+    idq.push_back((int64_t)qer.size());
+    lq.push_back((int32_t)n);
+    for (size_t k = 0; k < n; ++k) qer.push_back((uint8_t)(line[k] - 48));
+    for (long k = 0; k < nr; ++k) {
+      gb_bsw_alnreg a;
+      memset(&a, 0, sizeof(a));
+      long long rb = 0, re = 0;
+      if (!fgets(line.data(), (int)line.size(), f) ||
+          sscanf(line.data(), "%lld %lld %d %d %d %d %d %d %d %d %d %d %f", &rb, &re, &a.qb, &a.qe, &a.rid, &a.score,
+                 &a.truesc, &a.w, &a.seedcov, &a.seedlen0, &a.csub, &a.sub_n, &a.frac_rep) != 13) {
+        fprintf(stderr, "read %zu region %ld: expected thirteen numbers\n", lq.size() - 1, k);
+        return 1;
+      }
+      a.rb = rb, a.re = re;
+      max_rid = a.rid > max_rid ? a.rid : max_rid;
+      regs.push_back(a);
+    }
+    reg_off.push_back((int64_t)regs.size());
+  }
+  return 0;
+}
+
 // -finishregs: per read "bases n_regions", then per region thirteen numbers
 static int run_finishregs(const char *pac_file, const char *in_file, const char *out_file, const gb_bsw_params &gp,
                           const gb_bsw_reg_opt &ro, const RegsOpt &xo, const char *alt, const char *contigs) {
@@ -429,40 +480,13 @@ static int run_finishregs(const char *pac_file, const char *in_file, const char 
     fprintf(stderr, "Could not open file: %s\n", in_file);
     return 1;
   }
-  std::vector<uint8_t> qer;
-  std::vector<int64_t> idq, reg_off(1, 0);
-  std::vector<int32_t> lq;
-  std::vector<gb_bsw_alnreg> regs;
-  std::vector<char> line(1 << 12);
-  int max_rid = 0;
-  while (fgets(line.data(), (int)line.size(), f)) {
-    if (line[0] == '\n' || line[0] == '\r') continue;
-    size_t n = 0;
-    while (line[n] >= '0' && line[n] <= '4') ++n;
-    long nr = -1;
-    if (n < 1 || sscanf(line.data() + n, "%ld", &nr) != 1 || nr < 0) {
-      fprintf(stderr, "read %zu: expected \"bases n_regions\"\n", lq.size());
-      return 1;
-    }
-    idq.push_back((int64_t)qer.size());
-    lq.push_back((int32_t)n);
-    for (size_t k = 0; k < n; ++k) qer.push_back((uint8_t)(line[k] - 48));
-    for (long k = 0; k < nr; ++k) {
-      gb_bsw_alnreg a;
-      memset(&a, 0, sizeof(a));
-      long long rb = 0, re = 0;
-      if (!fgets(line.data(), (int)line.size(), f) ||
-          sscanf(line.data(), "%lld %lld %d %d %d %d %d %d %d %d %d %d %f", &rb, &re, &a.qb, &a.qe, &a.rid, &a.score,
-                 &a.truesc, &a.w, &a.seedcov, &a.seedlen0, &a.csub, &a.sub_n, &a.frac_rep) != 13) {
-        fprintf(stderr, "read %zu region %ld: expected thirteen numbers\n", lq.size() - 1, k);
-        return 1;
-      }
-      a.rb = rb, a.re = re;
-      max_rid = a.rid > max_rid ? a.rid : max_rid;
-      regs.push_back(a);
-    }
-    reg_off.push_back((int64_t)regs.size());
-  }
+  RegionFile R;
+  if (read_regions(f, R)) return 1;
+  std::vector<uint8_t> &qer = R.qer;
+  std::vector<int64_t> &idq = R.idq, &reg_off = R.reg_off;
+  std::vector<int32_t> &lq = R.lq;
+  std::vector<gb_bsw_alnreg> &regs = R.regs;
+  const int max_rid = R.max_rid;
   fclose(f);
   if (!n_contigs) n_contigs = (int64_t)max_rid + 1;
   FILE *info = out_file ? stdout : stderr;
@@ -502,10 +526,118 @@ static int run_finishregs(const char *pac_file, const char *in_file, const char 
   return 0;
 }
 
+// -materescue: a first line "pes low high failed" times four (FF, FR, RF, RR), or "pes auto" for gb_bsw_pestat's
+// over the file's own regions; then -finishregs' records, reads 2p and 2p + 1 being pair p
+static int run_materescue(const char *pac_file, const char *in_file, const char *out_file, const gb_bsw_params &gp,
+                          gb_bsw_pe_opt po, const char *contigs) {
+  gb_ref *ref = nullptr;
+  int st = gb_ref_load_pac(pac_file, &ref);
+  if (st) {
+    fprintf(stderr, "gb_ref_load_pac failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  int64_t l_pac = 0;
+  gb_ref_info(ref, &l_pac);
+  std::vector<int64_t> contig_end;
+  for (const char *c = contigs; c && *c;) {
+    char *e = nullptr;
+    contig_end.push_back(strtoll(c, &e, 10));
+    if (e == c) {
+      fprintf(stderr, "bsw: -contigs expects e1,e2,...\n");
+      return 1;
+    }
+    c = *e == ',' ? e + 1 : e;
+  }
+  FILE *f = fopen(in_file, "r");
+  if (!f) {
+    fprintf(stderr, "Could not open file: %s\n", in_file);
+    return 1;
+  }
+  struct gb_bsw_pestat pes[4];
+  memset(pes, 0, sizeof(pes));
+  char head[512];
+  bool pes_auto = false;
+  if (!fgets(head, sizeof(head), f) || strncmp(head, "pes", 3)) {
+    fprintf(stderr, "bsw: -materescue expects a first line \"pes low high failed (x4)\" or \"pes auto\"\n");
+    return 1;
+  }
+  if (!strncmp(head + 3, " auto", 5)) {
+    pes_auto = true;
+  } else if (sscanf(head + 3, "%d %d %d %d %d %d %d %d %d %d %d %d", &pes[0].low, &pes[0].high, &pes[0].failed, &pes[1].low,
+                    &pes[1].high, &pes[1].failed, &pes[2].low, &pes[2].high, &pes[2].failed, &pes[3].low, &pes[3].high,
+                    &pes[3].failed) != 12) {
+    fprintf(stderr, "bsw: the pes line needs twelve numbers\n");
+    return 1;
+  }
+  RegionFile R;
+  if (read_regions(f, R)) return 1;
+  fclose(f);
+  if (R.lq.size() % 2) {
+    fprintf(stderr, "bsw: -materescue needs an even number of reads (%zu)\n", R.lq.size());
+    return 1;
+  }
+  const int64_t n_contigs = contig_end.empty() ? (int64_t)R.max_rid + 1 : (int64_t)contig_end.size();
+  FILE *info = out_file ? stdout : stderr;
+  fprintf(info, "Number of input reads: %zu (%zu regions)\n", R.lq.size(), R.regs.size());
+  if (pes_auto && (st = gb_bsw_pestat(&po, l_pac, (int64_t)R.lq.size(), R.reg_off.data(), R.regs.data(), pes))) {
+    fprintf(stderr, "gb_bsw_pestat failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  for (int r = 0; r < 4; ++r)
+    fprintf(info, "pes %c%c: low %d high %d failed %d avg %.2f std %.2f\n", "FR"[r >> 1], "FR"[r & 1], pes[r].low,
+            pes[r].high, pes[r].failed, pes[r].avg, pes[r].std);
+  int64_t cap = (int64_t)R.regs.size();
+  for (size_t r = 0; r < R.lq.size(); ++r) {
+    const int64_t nm = R.reg_off[(r ^ 1) + 1] - R.reg_off[r ^ 1];
+    cap += 4 * (nm < po.max_matesw ? nm : po.max_matesw > 0 ? po.max_matesw : 0);
+  }
+  std::vector<gb_bsw_alnreg> out((size_t)cap + 1);
+  std::vector<int64_t> out_off(R.lq.size() + 1);
+  std::vector<int32_t> n_out(R.lq.size() + 1), n_sw(R.lq.size() / 2 + 1);
+  int64_t used = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  st = gb_bsw_mate_rescue(&gp, &po, pes, ref, contig_end.empty() ? nullptr : contig_end.data(), n_contigs, R.qer.data(),
+                          (int64_t)R.qer.size(), (int64_t)R.lq.size() / 2, R.idq.data(), R.lq.data(), R.reg_off.data(),
+                          R.regs.data(), out.data(), cap, out_off.data(), n_out.data(), n_sw.data(), &used);
+  const double sw_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (st) {
+    fprintf(stderr, "gb_bsw_mate_rescue failed (%d): %s\n", st, gb_last_error());
+    return 1;
+  }
+  float fetch = 0.f, dp = 0.f, region = 0.f, host = 0.f;
+  int32_t rounds = 0;
+  int64_t reqs = 0, aligned = 0;
+  gb_bsw_mate_rescue_timing(&fetch, &dp, &region, &host, &rounds, &reqs);
+  for (size_t p = 0; p < R.lq.size() / 2; ++p) aligned += n_sw[p];
+  fprintf(info, "Executed mate rescue (%d rounds, %lld requests, %lld alignments)...\n", rounds, (long long)reqs,
+          (long long)aligned);
+  fprintf(info, "Overall time = %0.3f s (%lld regions; fetch %.3f ms, DP %.3f ms, regions %.3f ms, host %.3f ms)\n", sw_s,
+          (long long)used, fetch, dp, region, host);
+  fprintf(info, "Total reads processed: %zu\n", R.lq.size());
+  FILE *o = out_file ? fopen(out_file, "w") : stdout;
+  if (!o) {
+    fprintf(stderr, "Could not open file: %s\n", out_file);
+    return 1;
+  }
+  for (size_t r = 0; r < R.lq.size(); ++r)
+    for (int32_t k = 0; k < n_out[r]; ++k) {
+      const gb_bsw_alnreg &a = out[(size_t)out_off[r] + (size_t)k];
+      fprintf(o, "%zu\t%lld\t%lld\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", r,
+              (long long)a.rb, (long long)a.re, a.qb, a.qe, a.rid, a.score, a.truesc, a.sub, a.alt_sc, a.csub, a.sub_n, a.w,
+              a.seedcov, a.secondary, a.secondary_all, a.seedlen0, a.n_comp, a.is_alt, a.mapq);
+    }
+  if (out_file) fclose(o);
+  gb_ref_destroy(ref);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   int w_match = 1, w_mismatch = 4, w_open = 6, w_extend = 1, w_ambig = -1, threads = 1, batch = 0, bits = 16;
   const char *pair_file = nullptr, *out_file = nullptr, *pac_file = nullptr, *contigs = nullptr;
   bool global = false, local = false, gencigar = false, chain2aln = false, mkchains = false, finishregs = false;
+  bool materescue = false;
+  gb_bsw_pe_opt po;
+  gb_bsw_pe_default_opt(&po);
   RegsOpt xo;
   int band = 100, zdrop_arg = 100, clip5 = 5, clip3 = 5;
   MkOpt mo;
@@ -523,6 +655,11 @@ int main(int argc, char **argv) {
     }
     if (!strcmp(argv[i], "-finishregs")) {
       finishregs = true;
+      --i;
+      continue;
+    }
+    if (!strcmp(argv[i], "-materescue")) {
+      materescue = true;
       --i;
       continue;
     }
@@ -553,6 +690,9 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-id0")) xo.id0 = atoll(argv[i + 1]);
     else if (!strcmp(argv[i], "-redun")) xo.redun = (float)atof(argv[i + 1]);
     else if (!strcmp(argv[i], "-primary5")) xo.primary5 = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-unpaired")) po.pen_unpaired = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-maxmatesw")) po.max_matesw = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "-maxins")) po.max_ins = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-maxgap")) mo.o.max_chain_gap = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-maxocc")) mo.o.max_occ = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "-minseed")) mo.o.min_seed_len = atoi(argv[i + 1]);
@@ -576,6 +716,23 @@ int main(int argc, char **argv) {
   if (global && local) {
     fprintf(stderr, "bsw: -local and -global exclude each other\n");
     return 1;
+  }
+  if (materescue) {
+    if (global || local || gencigar || chain2aln || mkchains || finishregs) {
+      fprintf(stderr, "bsw: -materescue excludes -global, -local, -gencigar, -chain2aln, -mkchains and -finishregs\n");
+      return 1;
+    }
+    if (!pac_file) {
+      fprintf(stderr, "bsw: -materescue needs -pac <file.pac>\n");
+      return 1;
+    }
+    gb_bsw_params gp;
+    gb_bsw_default_params(&gp);
+    gb_bsw_fill_scmat(w_match, w_mismatch, w_ambig, gp.mat);
+    po.a = w_match, po.b = w_mismatch, po.o_del = po.o_ins = w_open, po.e_del = po.e_ins = w_extend;
+    po.max_chain_gap = mo.o.max_chain_gap, po.min_seed_len = mo.o.min_seed_len;
+    po.mask_level = mo.o.mask_level, po.mask_level_redun = xo.redun;
+    return run_materescue(pac_file, pair_file, out_file, gp, po, contigs);
   }
   if (finishregs) {
     if (global || local || gencigar || chain2aln || mkchains) {

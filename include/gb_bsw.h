@@ -405,9 +405,9 @@ int gb_bsw_seeds2chains_timing(float *build_ms, float *filter_ms, float *emit_ms
  * MAPQ, and the reference never resets sub_n, so stage 1 adds to what is there (twice for a hit counted by
  * both passes of mem_mark_primary_se_core). Regions from gb_bsw_chain2aln carry 0 in all three.
  *
- * mem_reg2sam's selection loop (T, drop_ratio, the supplementary MAPQ cap), XA, infer_bw, the SAM text and
- * everything paired-end stay with the caller. The stage-1 primaries go into gb_bsw_gen_cigar_retry as they
- * are (rb, re, qb, qe, w, truesc).
+ * mem_reg2sam's selection loop (T, drop_ratio, the supplementary MAPQ cap), XA, infer_bw, the SAM text and, of
+ * the paired-end side, mem_pair and the paired MAPQ stay with the caller (mate rescue: gb_bsw_mate_rescue). The
+ * stage-1 primaries go into gb_bsw_gen_cigar_retry as they are (rb, re, qb, qe, w, truesc).
  *
  * params gives mat; the gap penalties of mem_patch_reg's alignment are opt's, as in the reference.
  * Read r has the query seq_buf_qer[idq[r] .. idq[r] + l_query[r]) and the regions regs[reg_off[r] ..
@@ -470,6 +470,76 @@ int gb_bsw_alnreg_from_regions(const gb_bsw_region *regions, int64_t n, const gb
  * of alignments, and the reads served on the host (all of them). */
 int gb_bsw_finish_regs_timing(float *dedup_ms, float *dp_ms, float *mark_ms, int32_t *dp_rounds, int64_t *dp_requests,
                               int64_t *host_reads);
+
+/* ---- mate rescue: the paired-end steps around ksw_align2 (tools/bwa/bwamem_pair.c), bit for bit and in
+ * the reference's order. Reads 2p and 2p + 1 are pair p.
+ *
+ * gb_bsw_pestat is mem_pestat (:46-109, with mem_infer_dir :23-30 and cal_sub :32-44) over the stage-0 regions
+ * of gb_bsw_finish_regs: per orientation (FF, FR, RF, RR) the bounds of a proper pair's distance, the mean and
+ * the deviation, or failed. It runs on the host, touches no device and prints nothing. avg and std carry
+ * the reference's bits (double arithmetic in its order, (int)(x + .499) truncating toward zero).
+ *
+ * gb_bsw_mate_rescue is the rescue loop of mem_sam_pe (:265-276) around mem_matesw (:111-180). Per pair the
+ * anchors of read i are its regions with score >= its best score - pen_unpaired, at most max_matesw of them,
+ * taken before any rescue; anchor j of read i looks for read !i in the windows the four orientations give,
+ * unless the orientation failed or read !i already has a region at a proper distance from the anchor. The
+ * window arithmetic, bns_fetch_seq's clip to the contig (or its reverse-strand mirror) holding the window's
+ * middle, the fetch from the pac, the mate's reverse complement, ksw_align2 and the region it gives run on
+ * the device, one round per anchor index j over all pairs, and the windows never leave it. The test above,
+ * the sorted insertion and mem_sort_dedup_patch without mem_patch_reg (the reference passes a null bns) run
+ * on the host between the rounds (GB_BSW_MATESW_THREADS threads, a number from 1 up, default up to 16).
+ * A window that is empty after the clamps to [0, 2 l_pac] does nothing (the reference reads an
+ * uninitialised rid there and then fails its length test).
+ *
+ * params gives mat; the gap penalties are opt's, as in gb_bsw_finish_regs, and xtra is gb_bsw_local_xtra's
+ * value with a = opt->a. Read r has the query seq_buf_qer[idq[r] .. idq[r] + l_query[r]) and the regions
+ * regs[reg_off[r] .. reg_off[r + 1]), which are never written. Read r's final list is out_regs[out_off[r] ..
+ * out_off[r] + n_out[r]), packed in read order; a rescued region has rid and is_alt of its anchor, secondary
+ * -1 and 0 in every field the reference leaves 0. n_sw[p] (may be NULL) is the sum of mem_matesw's return
+ * values for pair p: the alignments performed. The sum over the reads of n + 4 * min(anchors of the mate,
+ * max_matesw) always suffices for out_cap. With out_cap below the total the call returns GB_ERR_ARG, sets
+ * *out_used (may be NULL) to the count required, fills out_off and n_out and leaves out_regs untouched.
+ * n_pairs == 0 succeeds without a device. contig_end / n_contigs as in gb_bsw_chain2aln (NULL: one contig);
+ * n_contigs bounds rid in either case.
+ *
+ * Refused for the whole call with GB_ERR_ARG before any device work, nothing written, the read or the
+ * orientation named in gb_last_error(): what gb_bsw_finish_regs refuses about offsets, regions and rid;
+ * min_seed_len < 1, max_matesw < 0, pen_unpaired < 0, a < 1, min_seed_len * a above 65535; for an orientation
+ * that has not failed low < 0, high < low or high - low + the longest mate > GB_BSW_LOCAL_MAX_TLEN; a read
+ * whose mate has regions and that lies outside gb_bsw_local's domain for its xtra (l_query outside [1,
+ * GB_BSW_MAX_QLEN], a query outside seq_buf_qer, the GB_KSW_XBYTE rules, the penalties, the matrix);
+ * contig_end not increasing or not ending at l_pac. No exception leaves the call (GB_ERR_NOMEM).
+ *
+ * The requests of a round are cut into chunks whose windows stay under 256 MiB; GB_BSW_MATESW_CHUNK
+ * (requests per chunk, from 1 up) overrides that. */
+struct gb_bsw_pestat { /* mem_pestat_t (bwamem.h), 32 bytes; a tag only: the function has the name */
+  int32_t low, high, failed, pad;
+  double avg, std;
+};
+
+typedef struct gb_bsw_pe_opt { /* the mem_opt_t fields mem_pestat and mem_matesw read */
+  int32_t a, b, o_del, e_del, o_ins, e_ins, min_seed_len, max_chain_gap, pen_unpaired, max_matesw, max_ins;
+  float mask_level, mask_level_redun;
+} gb_bsw_pe_opt;
+/* 1, 4, 6, 1, 6, 1, 19, 10000, 17, 50, 10000, 0.50f, 0.95f (bwamem.c:50-86) */
+void gb_bsw_pe_default_opt(gb_bsw_pe_opt *o);
+
+/* n_reads is even; reg_off has n_reads + 1 entries. Refused with GB_ERR_ARG, pes untouched: n_reads odd or
+ * negative, offsets that decrease or do not start at 0, null arguments, mask_level not finite. */
+int gb_bsw_pestat(const gb_bsw_pe_opt *opt, int64_t l_pac, int64_t n_reads, const int64_t *reg_off,
+                  const gb_bsw_alnreg *regs, struct gb_bsw_pestat pes[4]);
+
+int gb_bsw_mate_rescue(const gb_bsw_params *params, const gb_bsw_pe_opt *opt, const struct gb_bsw_pestat pes[4],
+                       const gb_ref *ref, const int64_t *contig_end, int64_t n_contigs, const uint8_t *seq_buf_qer,
+                       int64_t qer_bytes, int64_t n_pairs, const int64_t *idq, const int32_t *l_query,
+                       const int64_t *reg_off, const gb_bsw_alnreg *regs, gb_bsw_alnreg *out_regs, int64_t out_cap,
+                       int64_t *out_off, int32_t *n_out, int32_t *n_sw, int64_t *out_used);
+
+/* Of the calling thread's last gb_bsw_mate_rescue: the device time of the window and fetch kernels (with the
+ * reverse complements), of the local DP and of the region kernel, summed over rounds and chunks; the host
+ * time of the bookkeeping between the rounds; the rounds that had a request, and the requests. */
+int gb_bsw_mate_rescue_timing(float *fetch_ms, float *dp_ms, float *region_ms, float *host_ms, int32_t *rounds,
+                              int64_t *requests);
 
 #ifdef __cplusplus
 }
