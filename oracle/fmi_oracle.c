@@ -44,6 +44,30 @@ typedef struct {
   int64_t k, l, s;
 } or_smem; /* SMEM, FMI_search.h:91-99 (non-DEBUG layout, 40 bytes) */
 
+/* Edge counters (test witnesses, per handle like bwt_calls; they change no result). They cost about
+ * a third of a cache-resident search, so the handles of fmi_oracle_share, which the threaded CPU
+ * baselines run on, do not count. Below, z is the sentinel row, sp = k and ep = k + s of a
+ * backwardExt call, and Yv means row & 63 == v. tests/fmi_util.py EDGE_NAMES lists the same
+ * counters in the same order. */
+enum {
+  OR_SP_EQ_Z, OR_SP_EQ_Z1, OR_EP_EQ_Z, OR_EP_EQ_Z1, /* sp / ep == z, z + 1 */
+  OR_SP_Y0, OR_SP_Y32, OR_SP_Y63, OR_EP_Y0, OR_EP_Y32, OR_EP_Y63,
+  OR_EP_EQ_N,                      /* ep == n: the interval ends at the last row */
+  OR_SAME_BLOCK, OR_DIFF_BLOCK,    /* sp >> 6 == / != ep >> 6 */
+  OR_SP_ZBLOCK_ABOVE,              /* sp in the sentinel's block, sp > z */
+  OR_EP_ZBLOCK_BELOW,              /* ep in the sentinel's block, ep <= z */
+  OR_T_AT_EDGE,                    /* extended base T and one of the four sentinel equalities */
+  OR_SP_EQ_Z_WIDE,                 /* sp == z with s >= 2: the only calls whose sentinel offset hangs on k <= z */
+  OR_EP_EQ_Z1_WIDE,                /* ep == z + 1 with s >= 2: likewise for k + s > z */
+  OR_SA_START_Z,                   /* SA walk that starts at z */
+  OR_SA_REACH_Z,                   /* ... that reaches z after >= 1 step */
+  OR_SA_STEP_FROM_Z1,              /* LF step taken from row z + 1 */
+  OR_SA_T_STEP,                    /* LF step over a T */
+  OR_SA_END_ROW0,                  /* walk that ends at sampled row 0 */
+  OR_SA_END_LAST,                  /* walk that ends at the last sampled row, (n >> 3) << 3 */
+  OR_NEDGE
+};
+
 typedef struct {
   int64_t n;        /* reference_seq_len in the file = |text| + 1 */
   int64_t count[5]; /* after the load-time +1 */
@@ -57,6 +81,8 @@ typedef struct {
   uint32_t *sa_ls_word;
   int64_t lf_steps;  /* SA-lookup LF steps (work accounting) */
   const int64_t *sa64; /* adopted packed samples (sa_ms_byte << 32 + sa_ls_word), or NULL */
+  int count_edges;         /* 1 on a handle of fmi_oracle_new; 0 on one of fmi_oracle_share, the timed path */
+  int64_t edges[OR_NEDGE]; /* which index-side edges the calls on this handle reached (fmi_oracle_edges) */
 } or_fmi;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -270,6 +296,29 @@ static inline int64_t get_occ(const or_fmi *f, int64_t pp, int c) {
 static or_smem backward_ext(or_fmi *f, or_smem smem, uint8_t a) {
   int64_t k[4], l[4], s[4];
   f->bwt_calls++;
+  if (f->count_edges) {
+    const int64_t sp = smem.k, ep = smem.k + smem.s, z = f->sentinel_index;
+    int64_t *e = f->edges;
+    const int at = (sp == z) | (sp == z + 1) | (ep == z) | (ep == z + 1);
+    e[OR_SP_EQ_Z] += sp == z;
+    e[OR_SP_EQ_Z1] += sp == z + 1;
+    e[OR_EP_EQ_Z] += ep == z;
+    e[OR_EP_EQ_Z1] += ep == z + 1;
+    e[OR_SP_Y0] += (sp & CP_MASK) == 0;
+    e[OR_SP_Y32] += (sp & CP_MASK) == 32;
+    e[OR_SP_Y63] += (sp & CP_MASK) == 63;
+    e[OR_EP_Y0] += (ep & CP_MASK) == 0;
+    e[OR_EP_Y32] += (ep & CP_MASK) == 32;
+    e[OR_EP_Y63] += (ep & CP_MASK) == 63;
+    e[OR_EP_EQ_N] += ep == f->n;
+    e[OR_SAME_BLOCK] += (sp >> CP_SHIFT) == (ep >> CP_SHIFT);
+    e[OR_DIFF_BLOCK] += (sp >> CP_SHIFT) != (ep >> CP_SHIFT);
+    e[OR_SP_ZBLOCK_ABOVE] += (sp >> CP_SHIFT) == (z >> CP_SHIFT) && sp > z;
+    e[OR_EP_ZBLOCK_BELOW] += (ep >> CP_SHIFT) == (z >> CP_SHIFT) && ep <= z;
+    e[OR_T_AT_EDGE] += a == 3 && at;
+    e[OR_SP_EQ_Z_WIDE] += sp == z && smem.s >= 2;
+    e[OR_EP_EQ_Z1_WIDE] += ep == z + 1 && smem.s >= 2;
+  }
   for (int b = 0; b < 4; b++) {
     int64_t sp = smem.k, ep = smem.k + smem.s;
     int64_t occ_sp = get_occ(f, sp, b), occ_ep = get_occ(f, ep, b);
@@ -653,7 +702,11 @@ void fmi_oracle_get_smems(or_fmi *f, const uint8_t *enc_qdb, int32_t numReads, i
 }
 
 /* ctypes-friendly handle API */
-or_fmi *fmi_oracle_new(void) { return (or_fmi *)calloc(1, sizeof(or_fmi)); }
+or_fmi *fmi_oracle_new(void) {
+  or_fmi *f = (or_fmi *)calloc(1, sizeof(or_fmi));
+  if (f) f->count_edges = 1;
+  return f;
+}
 void fmi_oracle_delete(or_fmi *f) {
   if (f) {
     fmi_oracle_free(f);
@@ -667,6 +720,8 @@ or_fmi *fmi_oracle_share(const or_fmi *f) {
   *g = *f;
   g->bwt_calls = 0;
   g->lf_steps = 0;
+  g->count_edges = 0;
+  memset(g->edges, 0, sizeof(g->edges));
   return g;
 }
 void fmi_oracle_unshare(or_fmi *g) { free(g); }
@@ -696,6 +751,10 @@ static inline int64_t sa_sample(const or_fmi *f, int64_t sp) {
  * except that reaching the sentinel row yields 0 whatever the step count (:1865-1869). */
 int64_t fmi_oracle_sa_entry(or_fmi *f, int64_t pos, int mode) {
   int64_t offset = 0, sp = pos;
+  const int64_t z = f->sentinel_index;
+  const int on = f->count_edges; /* 0 on a shared handle */
+  int64_t *const e = f->edges;
+  if (on) e[OR_SA_START_Z] += pos == z;
   while (sp & ((1 << SA_COMPX) - 1)) {
     const int64_t occ_id = sp >> CP_SHIFT, y = CP_BLOCK - (sp & CP_MASK) - 1;
     const uint64_t *oh = f->cp_occ[occ_id].one_hot_bwt_str;
@@ -705,11 +764,18 @@ int64_t fmi_oracle_sa_entry(or_fmi *f, int64_t pos, int mode) {
         b = c;
         break;
       }
-    if (b == 4) return mode ? 0 : offset;
+    if (b == 4) {
+      if (on) e[OR_SA_REACH_Z] += offset > 0;
+      return mode ? 0 : offset;
+    }
+    if (on) e[OR_SA_STEP_FROM_Z1] += sp == z + 1;
+    if (on) e[OR_SA_T_STEP] += b == 3;
     sp = f->count[b] + get_occ(f, sp, b);
     offset++;
     f->lf_steps++;
   }
+  if (on) e[OR_SA_END_ROW0] += sp == 0;
+  if (on) e[OR_SA_END_LAST] += sp == (f->n >> SA_COMPX) << SA_COMPX;
   return sa_sample(f, sp) + offset;
 }
 
@@ -734,3 +800,10 @@ void fmi_oracle_sa_lookup(or_fmi *f, const int64_t *rows, int64_t n, int mode, i
   for (int64_t i = 0; i < n; i++) out[i] = fmi_oracle_sa_entry(f, rows[i], mode);
 }
 int64_t fmi_oracle_lf_steps(const or_fmi *f) { return f->lf_steps; }
+
+/* Read and clear the edge counters: writes min(cap, OR_NEDGE) of them, returns OR_NEDGE. */
+int fmi_oracle_edges(or_fmi *f, int64_t *out, int cap) {
+  for (int i = 0; i < OR_NEDGE && i < cap; i++) out[i] = f->edges[i];
+  memset(f->edges, 0, sizeof(f->edges));
+  return OR_NEDGE;
+}

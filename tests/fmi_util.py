@@ -12,6 +12,14 @@ SMEM_DTYPE = np.dtype([("rid", "<u4"), ("m", "<u4"), ("n", "<u4"), ("pad", "<u4"
                        ("k", "<i8"), ("l", "<i8"), ("s", "<i8")])
 assert SMEM_DTYPE.itemsize == 40
 
+# oracle/fmi_oracle.c's edge counters, in its order (z = sentinel row, sp = k, ep = k + s of a
+# backwardExt call; the sa_* ones count events of fmi_oracle_sa_entry's LF walks)
+EDGE_NAMES = ("sp_eq_z", "sp_eq_z1", "ep_eq_z", "ep_eq_z1",
+              "sp_y0", "sp_y32", "sp_y63", "ep_y0", "ep_y32", "ep_y63",
+              "ep_eq_n", "same_block", "diff_block", "sp_zblock_above", "ep_zblock_below", "t_at_edge",
+              "sp_eq_z_wide", "ep_eq_z1_wide",
+              "sa_start_z", "sa_reach_z", "sa_step_from_z1", "sa_t_step", "sa_end_row0", "sa_end_last")
+
 
 def _decl(lib):
     vp, i64 = ctypes.c_void_p, ctypes.c_int64
@@ -36,6 +44,8 @@ def _decl(lib):
     lib.fmi_oracle_sa_entries.restype = i64
     lib.fmi_oracle_lf_steps.argtypes = [vp]
     lib.fmi_oracle_lf_steps.restype = i64
+    lib.fmi_oracle_edges.argtypes = [vp, vp, ctypes.c_int]
+    lib.fmi_oracle_edges.restype = ctypes.c_int
     i32 = ctypes.c_int32
     lib.fmi_oracle_get_smems.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.fmi_oracle_get_smems.restype = None
@@ -158,6 +168,12 @@ class OracleIndex:
 
     def lf_steps(self):
         return self.lib.fmi_oracle_lf_steps(self.h)
+
+    def edges(self):
+        """The edge counters of the calls on this handle since the last edges(), by name; clears them."""
+        out = np.zeros(len(EDGE_NAMES), np.int64)
+        assert self.lib.fmi_oracle_edges(self.h, out.ctypes.data, len(out)) == len(EDGE_NAMES)
+        return dict(zip(EDGE_NAMES, out.tolist()))
 
     def sa_entries_threaded(self, smems, threads, max_occ=500, mode=1):
         """sa_entries over `threads` OS threads (shared tables); returns (coordinates, LF steps)."""
