@@ -17,7 +17,7 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize
+.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -116,6 +116,16 @@ tests/_build/matesw_host_check: tests/cpp/matesw_host_check.cpp $(MATESW_CHECK_S
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(MATESW_CHECK_SRCS) \
+	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the host utilities of gb_common.h (fork-join, thread count, per-thread workspaces, round-up) under the
+# same sanitizers: no HIP call is made. Not part of `all`.
+hostutil-sanitize: tests/_build/hostutil_check
+	tests/_build/hostutil_check
+tests/_build/hostutil_check: tests/cpp/hostutil_check.cpp $(CSRC)/gb_common.cpp $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/gb_common.cpp \
 	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:

@@ -32,6 +32,7 @@
 #include "../../include/gb_bsw.h"
 #include "bsw_internal.h"
 #include "gb_common.h"
+#include "gb_common_wave.h"
 
 static_assert(sizeof(gb_seqpair) == 72, "gb_seqpair must match SeqPair (bandedSWA.h:92-101)");
 
@@ -58,19 +59,6 @@ struct Args {
   int8_t mat[28];
 };
 
-// wave-wide inclusive max scan (Hillis-Steele in 16-lane rows, then row broadcasts)
-__device__ __forceinline__ int scan_max(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x142, 0xA, 0xF, false));  // row_bcast:15
-  v = max(v, __builtin_amdgcn_update_dpp(kNeg, v, 0x143, 0xC, 0xF, false));  // row_bcast:31
-  return v;
-}
-__device__ __forceinline__ int shr1(int v, int lane0) {
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xF, 0xF, false);  // wave_shr:1
-}
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 
 template <int K>
@@ -135,7 +123,7 @@ __device__ __forceinline__ void extend(const Args &A, const Pair &P, const int8_
       lpx[c] = lp;
       lp = max(lp, g[c]);
     }
-    const int lex = shr1(scan_max(lp), kNeg);
+    const int lex = gb::wave_shr1(gb::scan_max<kNeg>(lp), kNeg);
     int hm = -1;
 #pragma unroll
     for (int c = 0; c < K; ++c) {
@@ -144,7 +132,7 @@ __device__ __forceinline__ void extend(const Args &A, const Pair &P, const int8_
       En[c] = max(max(E[c] - e_del, M[c] - oe_del), 0);  // E(i+1,j)
       if (inb[c]) hm = max(hm, h[c]);
     }
-    const int m = max(__builtin_amdgcn_readlane(scan_max(hm), 63), 0);
+    const int m = max(gb::wave_max<kNeg>(hm), 0);
     int mj = -1;
     if (m > 0) {  // last column reaching the row maximum (bandedSWA.cpp:203-204)
       int jl = -1;
@@ -157,7 +145,7 @@ __device__ __forceinline__ void extend(const Args &A, const Pair &P, const int8_
     // eh[j].h <- H(i,j-1) for j in (beg, end], eh[beg].h <- first column, eh[j].e <- E(i+1,j),
     // eh[end].e <- 0 (bandedSWA.cpp:195-197,217)
     const int wlo = min(beg, end);
-    const int hprev = shr1(h[K - 1], 0);
+    const int hprev = gb::wave_shr1(h[K - 1], 0);
 #pragma unroll
     for (int c = 0; c < K; ++c) {
       const int j = lane * K + c;
@@ -715,14 +703,8 @@ int bsw_batch_plan(gb_bsw_batch *B, const gb_bsw_params *params, const gb_seqpai
     }
   };
   const int nth = n >= (1 << 17) ? (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-  if (nth == 1) {
-    plan(0, n);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; t++) th.emplace_back(plan, n * t / nth, n * (t + 1) / nth);
-    plan(0, n / nth);
-    for (auto &x : th) x.join();
-  }
+  if (const int st = gb::parallel("gb_bsw_batch_create", nth, [&](int t) { plan(n * t / nth, n * (t + 1) / nth); }))
+    return st;
   if (bad.load() < n) {
     const int64_t p = bad.load();
     const gb_seqpair &s = pairs[p];
@@ -1023,10 +1005,9 @@ int gb_bsw_batch_results(gb_bsw_batch *B, gb_seqpair *pairs, int32_t *out6, int3
         }
       };
       const size_t nth = n >= (1u << 17) ? std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-      std::vector<std::thread> th;
-      for (size_t t = 1; t < nth; t++) th.emplace_back(scatter, n * t / nth, n * (t + 1) / nth);
-      scatter(0, n / nth);
-      for (auto &x : th) x.join();
+      const int st = gb::parallel("gb_bsw_batch_results", (int)nth,
+                                  [&](int t) { scatter(n * t / nth, n * (t + 1) / nth); });
+      if (st) return st;
     }
   }
   if (n && cells) GB_HIP(hipMemcpy(cells, B->d_cells, n * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1062,9 +1043,9 @@ namespace {
 // the results back by one D2H copy on the calling thread's stream.
 constexpr int64_t kSmallCall = 16384;  // pairs; GB_BSW_SMALL overrides (0 = never)
 
-struct SmallWs {
+struct SmallWs {  // the calling thread's, through gb::thread_ws
   int device = -1, num_cus = 256;
-  hipStream_t stream = nullptr;
+  gb::Stream stream;
   gb::PinnedBuf<uint8_t> h;
   gb::DevBuf<uint8_t> d;
 };
@@ -1073,8 +1054,6 @@ int64_t small_call_limit() {
   const char *e = getenv("GB_BSW_SMALL");  // read per call: tests switch paths inside one process
   return e ? (int64_t)atoll(e) : kSmallCall;
 }
-
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 struct SmallReq {
   const gb_bsw_params *params;
@@ -1086,22 +1065,20 @@ struct SmallReq {
   bool done = false;
 };
 
-SmallWs *small_ws(int dev, int *st) {
-  // one workspace per (host thread, device); never freed (see gb_bsw_get_scores16_ex)
-  thread_local std::vector<SmallWs *> wss;
-  for (auto *w : wss)
-    if (w->device == dev) return w;
-  auto *W = new SmallWs();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    gb::set_error("getScores16 workspace: %s", hipGetErrorString(e));
-    *st = GB_ERR_HIP;
-    return nullptr;
-  }
-  wss.push_back(W);
-  return W;
+int small_ws(int dev, SmallWs **out) {
+  return gb::thread_ws(dev, out, [](int dev, SmallWs **out) {
+    auto *W = new SmallWs();
+    W->device = dev;
+    hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = W->stream.create();
+    if (e != hipSuccess) {
+      gb::set_error("getScores16 workspace: %s", hipGetErrorString(e));
+      delete W;
+      return GB_ERR_HIP;
+    }
+    *out = W;
+    return GB_OK;
+  });
 }
 
 // One launch for a group of requests with the same parameters: their pairs are concatenated (and
@@ -1120,9 +1097,11 @@ int small_group(SmallWs *W, const std::vector<SmallReq *> &g) {
     }
   }
   // staging / device layout: [Pair n | list n | ctl 16 B | tgt | qry] (uploaded) [out6 n | cells n]
-  const size_t o_list = up16(sizeof(gbbsw::Pair) * (size_t)n), o_ctl = o_list + up16(4 * (size_t)n),
-               o_tgt = o_ctl + 16, o_qry = o_tgt + up16((size_t)tb), up_bytes = o_qry + up16((size_t)qb),
-               o_out = up_bytes, o_cells = o_out + up16(24 * (size_t)n), d_bytes = o_cells + up16(4 * (size_t)n);
+  using gb::round_up;
+  const size_t nz = (size_t)n, o_list = round_up(sizeof(gbbsw::Pair) * nz, 16), o_ctl = o_list + round_up(4 * nz, 16),
+               o_tgt = o_ctl + 16, o_qry = o_tgt + round_up((size_t)tb, 16),
+               up_bytes = o_qry + round_up((size_t)qb, 16), o_out = up_bytes,
+               o_cells = o_out + round_up(24 * nz, 16), d_bytes = o_cells + round_up(4 * nz, 16);
   // both grow to twice the need, at least 1 MiB
   const size_t h_bytes = std::max(up_bytes, d_bytes - o_out);
   int st = W->h.reserve(h_bytes, std::max<size_t>(2 * h_bytes, 1 << 20));
@@ -1235,9 +1214,8 @@ int small_call(const gb_bsw_params *params, gb_seqpair *pairs, int64_t n, const 
   }
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  int st = GB_OK;
-  SmallWs *W = small_ws(dev, &st);
-  if (!W) return st;
+  SmallWs *W = nullptr;
+  if (const int st = small_ws(dev, &W)) return st;
   SmallReq me{params, pairs, n, ref, qer, total_cells};
   Combiner &C = combiner(dev);
   std::unique_lock<std::mutex> lk(C.m);
@@ -1274,22 +1252,11 @@ int small_call(const gb_bsw_params *params, gb_seqpair *pairs, int64_t n, const 
   return me.status;
 }
 
-// The calling thread's cached batch on the current device. Never freed (freeing at thread exit could
-// run after the HIP runtime is torn down).
+// The calling thread's cached batch on the current device.
 int cached_batch(gb_bsw_batch **out) {
-  thread_local std::vector<std::pair<int, gb_bsw_batch *>> ws;
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  for (auto &w : ws)
-    if (w.first == dev) {
-      *out = w.second;
-      return GB_OK;
-    }
-  gb_bsw_batch *B = nullptr;
-  if (int st = bsw_batch_new(&B)) return st;
-  ws.emplace_back(dev, B);
-  *out = B;
-  return GB_OK;
+  return gb::thread_ws(dev, out, [](int, gb_bsw_batch **B) { return bsw_batch_new(B); });
 }
 
 }  // namespace
@@ -1329,7 +1296,6 @@ int gb_bsw_get_scores16_ex(const gb_bsw_params *params, gb_seqpair *pairs, int64
   if (n > 0 && n <= small_call_limit()) return small_call(params, pairs, n, ref, ref_bytes, qer, qer_bytes, total_cells);
   // one cached batch per (host thread, device): the reference calls getScores16 once per batch of
   // 512 pairs (main_banded.cpp:896-909), so streams, events and buffers are reused across calls.
-  // Never freed (freeing at thread exit could run after the HIP runtime is torn down).
   gb_bsw_batch *B = nullptr;
   int st = cached_batch(&B);
   if (st) return st;

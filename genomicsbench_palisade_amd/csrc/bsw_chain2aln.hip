@@ -272,10 +272,10 @@ __global__ __launch_bounds__(64) void bsw_c2a_emit_kernel(DevArgs A) {
   for (int i = 0; i < n; ++i) A.out[o + i] = A.cand[keep[i]];
 }
 
-struct CWs {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct CWs {  // the calling thread's, through gb::thread_ws
   int device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {};  // gather, finish, filter begin / end
+  gb::Stream stream;
+  gb::Event ev[6];  // gather, finish, filter begin / end
   gb::PinnedBuf<uint8_t> h_in;
   // host scratch that is read back here lives in ordinary memory (reads of page-locked memory are slow),
   // and in the workspace, so that a call does not fault its pages in again
@@ -291,35 +291,22 @@ struct CWs {  // one per (calling thread, device), never freed (see gb_bsw_get_s
   float gather_ms = 0.f, ext_ms[4] = {0.f, 0.f, 0.f, 0.f}, finish_ms = 0.f, filter_ms = 0.f;
 };
 
-thread_local std::vector<CWs *> g_ws;
-
-CWs *find_ws(int dev) {
-  for (auto *w : g_ws)
-    if (w->device == dev) return w;
-  return nullptr;
-}
-
 int get_ws(int dev, CWs **out) {
-  if ((*out = find_ws(dev))) return GB_OK;
-  auto *W = new CWs();
-  W->device = dev;
-  hipError_t e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e != hipSuccess) {
-    gb::set_error("gb_bsw_chain2aln workspace: %s", hipGetErrorString(e));
+  return gb::thread_ws(dev, out, [](int dev, CWs **out) {
+    auto *W = new CWs();
+    W->device = dev;
+    hipError_t e = W->stream.create();
     for (auto &ev : W->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    if (W->stream) (void)hipStreamDestroy(W->stream);
-    delete W;
-    return GB_ERR_HIP;
-  }
-  g_ws.push_back(W);
-  *out = W;
-  return GB_OK;
+      if (e == hipSuccess) e = ev.create();
+    if (e != hipSuccess) {
+      gb::set_error("gb_bsw_chain2aln workspace: %s", hipGetErrorString(e));
+      delete W;
+      return GB_ERR_HIP;
+    }
+    *out = W;
+    return GB_OK;
+  });
 }
-
-inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 struct Window {  // a chain's window after the clamps and the clip (bwamem.c:642-659)
   int64_t rmax0, rmax1;
@@ -379,7 +366,7 @@ int make_plan(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen_clip3,
     GB_ARG((int64_t)lq * std::max(amax, 1) < (1 << 30), "%s: read %lld: l_query = %d times the match score overflows", who,
            (long long)r, lq);
     GB_ARG(idq[r] >= 0 && idq[r] + lq <= qer_bytes, "%s: read %lld lies outside the query buffer", who, (long long)r);
-    int64_t rbytes = 2 * up(lq, 4);
+    int64_t rbytes = 2 * gb::round_up<int64_t>(lq, 4);
     for (int64_t c = rco[r]; c < rco[r + 1]; ++c) {
       const gb_bsw_seed *cs = seeds + cso[c];
       const int n = (int)std::min<int64_t>(cso[c + 1] - cso[c], INT32_MAX);
@@ -442,7 +429,7 @@ int make_plan(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen_clip3,
       GB_ARG(rmax1 - rmax0 < (1ll << 31), "%s: read %lld chain %lld: a window of %lld bases", who, (long long)r,
              (long long)c, (long long)(rmax1 - rmax0));
       P->win[(size_t)c] = Window{rmax0, rmax1};
-      rbytes += 2 * up(rmax1 - rmax0, 16);
+      rbytes += 2 * gb::round_up<int64_t>(rmax1 - rmax0, 16);
       // bwamem.c:662-665: by increasing score << 32 | index, that is by score and, among equal scores,
       // by index; the keys are distinct, so any sort gives the reference's order (chains are short:
       // insertion)
@@ -474,12 +461,8 @@ int make_plan(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen_clip3,
         return;
       }
   };
-  {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; ++t) th.emplace_back(plan_range, n_reads * t / nth, n_reads * (t + 1) / nth);
-    plan_range(0, n_reads / nth);
-    for (auto &x : th) x.join();
-  }
+  if (const int st = gb::parallel(who, nth, [&](int t) { plan_range(n_reads * t / nth, n_reads * (t + 1) / nth); }))
+    return st;
   if (bad.load() < n_reads) return plan_read(bad.load());
   int64_t bytes = 0;
   P->cuts.push_back(0);
@@ -498,7 +481,7 @@ struct Blob {  // offsets of the chunk's uploaded arrays inside one staging bloc
   int64_t size = 0;
   int64_t take(int64_t bytes) {
     const int64_t at = size;
-    size += up(std::max<int64_t>(bytes, 1), 16);
+    size += gb::round_up<int64_t>(std::max<int64_t>(bytes, 1), 16);
     return at;
   }
 };
@@ -506,25 +489,21 @@ struct Blob {  // offsets of the chunk's uploaded arrays inside one staging bloc
 // The descriptors of one side's first round: fill(k, &pair) returns whether seed k has that side. Big
 // chunks are cut into ranges that threads count, then fill at their offsets, so the order is by seed.
 template <class Fill>
-void build_round(int64_t ns, Fill fill, std::vector<int32_t> *list, std::vector<gb_seqpair> *sp) {
+int build_round(int64_t ns, Fill fill, std::vector<int32_t> *list, std::vector<gb_seqpair> *sp) {
+  const char *who = "gb_bsw_chain2aln";
   const int nth = ns >= (1 << 16) ? (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
   std::vector<int64_t> at((size_t)nth + 1, 0);
-  auto run = [&](auto body) {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; ++t) th.emplace_back(body, t);
-    body(0);
-    for (auto &x : th) x.join();
-  };
-  run([&](int t) {
+  int st = gb::parallel(who, nth, [&](int t) {
     gb_seqpair x{};
     int64_t n = 0;
     for (int64_t k = ns * t / nth; k < ns * (t + 1) / nth; ++k) n += fill(k, &x) ? 1 : 0;
     at[(size_t)t + 1] = n;
   });
+  if (st) return st;
   for (int t = 0; t < nth; ++t) at[(size_t)t + 1] += at[(size_t)t];
   list->resize((size_t)at[(size_t)nth]);
   sp->resize((size_t)at[(size_t)nth]);
-  run([&](int t) {
+  return gb::parallel(who, nth, [&](int t) {
     int64_t o = at[(size_t)t];
     gb_seqpair x{};
     for (int64_t k = ns * t / nth; k < ns * (t + 1) / nth; ++k)
@@ -616,8 +595,8 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
     const int64_t o_chain = B.take(nc * (int64_t)sizeof(ChainItem)), o_read = B.take(nr * (int64_t)sizeof(ReadItem)),
                   o_cso = B.take((nc + 1) * 8), o_rco = B.take((nr + 1) * 8), o_sc = B.take(ns * 4),
                   o_srt = B.take(ns * 4), o_seed = B.take(ns * (int64_t)sizeof(gb_bsw_seed));
-    for (int64_t r = r0; r < r1; ++r) q_half += up(l_query[r], 4);
-    q_half = up(std::max<int64_t>(q_half, 1), 16);
+    for (int64_t r = r0; r < r1; ++r) q_half += gb::round_up<int64_t>(l_query[r], 4);
+    q_half = gb::round_up<int64_t>(std::max<int64_t>(q_half, 1), 16);
     const int64_t o_qry = B.take(q_half);
     if ((st = W->h_in.reserve((size_t)B.size, (size_t)B.size * 2))) return st;
     if ((st = W->d_in.reserve((size_t)B.size, (size_t)B.size * 2))) return st;
@@ -632,11 +611,11 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
     for (int64_t r = r0; r < r1; ++r) {
       hr[r - r0] = ReadItem{qo, l_query[r], 0};
       std::memcpy(h + o_qry + qo, qer + idq[r], (size_t)l_query[r]);
-      qo += up(l_query[r], 4);
+      qo += gb::round_up<int64_t>(l_query[r], 4);
       hrco[r - r0] = rco[r] - c0;
       for (int64_t c = rco[r]; c < rco[r + 1]; ++c) {
         const Window &wn = P.win[(size_t)c];
-        const int64_t L = wn.rmax1 - wn.rmax0, Lp = up(L, 16);
+        const int64_t L = wn.rmax1 - wn.rmax0, Lp = gb::round_up<int64_t>(L, 16);
         hc[c - c0] = ChainItem{wn.rmax0, tgt_bytes, tgt_bytes + Lp, (int32_t)L, (int32_t)(r - r0)};
         tgt_bytes += 2 * Lp;
         hcso[c - c0] = cso[c] - s0;
@@ -692,7 +671,7 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
     std::vector<int32_t> &list = W->list, &again = W->again, &sc0 = W->sc0;  // sc0: the score the right side starts from
     std::vector<gb_seqpair> &sp = W->sp, &sp2 = W->sp2;
     sc0.resize((size_t)nsz);
-    build_round(ns, [&](int64_t k, gb_seqpair *x) {
+    st = build_round(ns, [&](int64_t k, gb_seqpair *x) {
       const gb_bsw_seed &s = seeds[s0 + k];
       sc0[(size_t)k] = s.len * opt.a;
       if (!s.qbeg) return false;
@@ -704,6 +683,7 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
       x->h0 = s.len * opt.a;
       return true;
     }, &list, &sp);
+    if (st) return st;
     mark("pairs_l");
     GB_HIP(hipStreamSynchronize(W->stream));  // the extension kernels run on the batch's own streams
     mark("gather");
@@ -727,7 +707,7 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
     if ((st = run_round(W, params, 0, opt.w << 1, pen_clip5, again, sp2, tgt_cap, 2 * q_half, &W->ext_ms[1]))) return st;
     for (size_t k = 0; k < again.size(); ++k) sc0[(size_t)again[k]] = W->h_out6[6 * k];
     mark("left");
-    build_round(ns, [&](int64_t k, gb_seqpair *x) {
+    st = build_round(ns, [&](int64_t k, gb_seqpair *x) {
       const gb_bsw_seed &s = seeds[s0 + k];
       const ChainItem &c = hc[hsc[k]];
       const ReadItem &rd = hr[c.read];
@@ -738,6 +718,7 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
       x->h0 = sc0[(size_t)k];
       return true;
     }, &list, &sp);
+    if (st) return st;
     mark("pairs_r");
     if ((st = run_round(W, params, 1, opt.w, pen_clip3, list, sp, tgt_cap, 2 * q_half, &W->ext_ms[2]))) return st;
     second(sc0.data());  // prev is the left score (bwamem.c:771,799)
@@ -807,7 +788,7 @@ int gb_bsw_chain2aln(const gb_bsw_params *params, int32_t pen_clip5, int32_t pen
 int gb_bsw_chain2aln_timing(float *gather_ms, float ext_ms[4], float *finish_ms, float *filter_ms) {
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  gbc2a::CWs *W = gbc2a::find_ws(dev);
+  gbc2a::CWs *W = gb::find_thread_ws<gbc2a::CWs>(dev);
   if (!W) {
     gb::set_error("gb_bsw_chain2aln_timing: no gb_bsw_chain2aln call on this thread and device");
     return GB_ERR_STATE;

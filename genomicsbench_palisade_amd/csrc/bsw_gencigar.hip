@@ -188,9 +188,9 @@ __global__ __launch_bounds__(64) void bsw_gencigar_md_kernel(MdArgs A) {
   o[2] = mm;
 }
 
-struct GWs {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct GWs {  // the calling thread's, through gb::thread_ws
   int device = -1;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // fetch begin / end, md begin / end
+  gb::Event ev[4];  // fetch begin / end, md begin / end
   gb::DevBuf<uint8_t> d_tgt, d_qry, d_rev;
   gb::DevBuf<FetchItem> d_items;
   gb::DevBuf<int32_t> d_score, d_md3;
@@ -200,35 +200,25 @@ struct GWs {  // one per (calling thread, device), never freed (see gb_bsw_get_s
   float fetch_ms = 0.f, fill_ms = 0.f, walk_ms = 0.f, md_ms = 0.f;
 };
 
-thread_local std::vector<GWs *> g_gws;
-
-GWs *find_gws(int dev) {
-  for (auto *w : g_gws)
-    if (w->device == dev) return w;
-  return nullptr;
-}
-
 int get_gws(int dev, GWs **out) {
-  if ((*out = find_gws(dev))) return GB_OK;
-  auto *G = new GWs();
-  G->device = dev;
-  hipError_t e = hipSuccess;
-  for (auto &ev : G->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  int st = GB_ERR_HIP;
-  if (e == hipSuccess)
-    st = G->d_mctl.reserve(4);
-  else
-    gb::set_error("gb_bsw_gen_cigar workspace: %s", hipGetErrorString(e));
-  if (st) {
+  return gb::thread_ws(dev, out, [](int dev, GWs **out) -> int {
+    auto *G = new GWs();
+    G->device = dev;
+    hipError_t e = hipSuccess;
     for (auto &ev : G->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    delete G;
-    return st;
-  }
-  g_gws.push_back(G);
-  *out = G;
-  return GB_OK;
+      if (e == hipSuccess) e = ev.create();
+    int st = GB_ERR_HIP;
+    if (e == hipSuccess)
+      st = G->d_mctl.reserve(4);
+    else
+      gb::set_error("gb_bsw_gen_cigar workspace: %s", hipGetErrorString(e));
+    if (st) {
+      delete G;
+      return st;
+    }
+    *out = G;
+    return GB_OK;
+  });
 }
 
 // Upload on first use; afterwards the reference belongs to that device.
@@ -593,7 +583,7 @@ int deliver(const char *who, const std::vector<uint32_t> &cig, const std::vector
 void reset_timing() {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return;
-  if (GWs *G = find_gws(dev)) G->fetch_ms = G->fill_ms = G->walk_ms = G->md_ms = 0.f;
+  if (GWs *G = gb::find_thread_ws<GWs>(dev)) G->fetch_ms = G->fill_ms = G->walk_ms = G->md_ms = 0.f;
 }
 
 }  // namespace gbgc
@@ -814,7 +804,7 @@ int gb_bsw_gen_cigar_timing(float *fetch_ms, float *fill_ms, float *walk_ms, flo
   GB_ARG(fetch_ms && fill_ms && walk_ms && md_ms, "gb_bsw_gen_cigar_timing: null argument");
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  const gbgc::GWs *G = gbgc::find_gws(dev);
+  const gbgc::GWs *G = gb::find_thread_ws<gbgc::GWs>(dev);
   if (!G) {
     gb::set_error("gb_bsw_gen_cigar_timing: gb_bsw_gen_cigar has not run on this thread and device");
     return GB_ERR_STATE;

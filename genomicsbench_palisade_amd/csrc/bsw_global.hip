@@ -30,6 +30,7 @@
 #include "../../include/gb_bsw.h"
 #include "bsw_global_internal.h"
 #include "gb_common.h"
+#include "gb_common_wave.h"
 
 static_assert(sizeof(gb_bsw_gpair) == 48, "gb_bsw_gpair is 48 bytes (include/gb_bsw.h)");
 
@@ -61,20 +62,6 @@ struct WalkArgs {
   unsigned int *pool_used;  // operations reserved so far
   unsigned int *bad;        // lowest pair index whose walk hit the step clamp
 };
-
-// wave-wide inclusive max scan (Hillis-Steele in 16-lane rows, then row broadcasts)
-__device__ __forceinline__ int scan_max(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x142, 0xA, 0xF, false));  // row_bcast:15
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x143, 0xC, 0xF, false));  // row_bcast:31
-  return v;
-}
-__device__ __forceinline__ int shr1(int v, int lane0) {
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xF, 0xF, false);  // wave_shr:1
-}
 
 template <int K, bool DIR>
 __device__ __forceinline__ void fill(const FillArgs &A, const Pair &P, const int8_t *smat, int lane, int32_t *o4) {
@@ -142,7 +129,7 @@ __device__ __forceinline__ void fill(const FillArgs &A, const Pair &P, const int
       lpx[c] = lp;
       lp = max(lp, inb ? M[c] - oe_ins + ej[c] : kNegInf);
     }
-    const int lex = shr1(scan_max(lp), kNegInf);
+    const int lex = gb::wave_shr1(gb::scan_max<kNegInf>(lp), kNegInf);
     int h[K], En[K];
     uint32_t word = 0;
 #pragma unroll
@@ -167,7 +154,7 @@ __device__ __forceinline__ void fill(const FillArgs &A, const Pair &P, const int
     }
     // eh[j].h <- H(i,j-1) for j in (beg, end], eh[beg].h <- first column, eh[j].e <- E(i+1,j),
     // eh[end].e <- minus infinity (ksw.c:549,560,585)
-    const int hprev = shr1(h[K - 1], 0);
+    const int hprev = gb::wave_shr1(h[K - 1], 0);
 #pragma unroll
     for (int c = 0; c < K; ++c) {
       const int j = lane * K + c;
@@ -311,38 +298,27 @@ int64_t dir_words_limit() {  // GB_BSW_GLOBAL_DIR_WORDS (tests: many chunks from
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kDirWords)) : kDirWords;
 }
 
-thread_local std::vector<Ws *> g_ws;
-
-Ws *find_ws(int dev) {
-  for (auto *w : g_ws)
-    if (w->device == dev) return w;
-  return nullptr;
-}
-
-int get_ws(int dev, Ws **out) {
-  if ((*out = find_ws(dev))) return GB_OK;
+static int make_ws(int dev, Ws **out) {
   auto *W = new Ws();
   W->device = dev;
   hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = W->stream.create();
   for (auto &ev : W->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = ev.create();
   int st = GB_ERR_HIP;
   if (e == hipSuccess)
     st = W->d_ctl.reserve(4);
   else
     gb::set_error("gb_bsw_global workspace: %s", hipGetErrorString(e));
   if (st) {
-    for (auto &ev : W->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    if (W->stream) (void)hipStreamDestroy(W->stream);
     delete W;
     return st;
   }
-  g_ws.push_back(W);
   *out = W;
   return GB_OK;
 }
+
+int get_ws(int dev, Ws **out) { return gb::thread_ws(dev, out, make_ws); }
 
 // Every refusal of include/gb_bsw.h, before any device work.
 int validate(const gb_bsw_params *params, const gb_bsw_gpair *pairs, int64_t n, const uint8_t *ref, int64_t ref_bytes,
@@ -390,7 +366,7 @@ int gb_bsw_global_timing(float *fill_ms, float *walk_ms) {
   GB_ARG(fill_ms && walk_ms, "gb_bsw_global_timing: null argument");
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  const gbbswg::Ws *W = gbbswg::find_ws(dev);
+  const gbbswg::Ws *W = gb::find_thread_ws<gbbswg::Ws>(dev);
   if (!W) {
     gb::set_error("gb_bsw_global_timing: gb_bsw_global has not run on this thread and device");
     return GB_ERR_STATE;

@@ -23,10 +23,10 @@ __host__ __device__ inline int row_words(int qlen) {  // lanes owning a query co
   return (qlen + K - 1) / K;
 }
 
-struct Ws {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct Ws {  // the calling thread's, through gb::thread_ws
   int device = -1, num_cus = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  gb::Stream stream;
+  gb::Event ev[3];
   gb::DevBuf<uint8_t> d_tgt, d_qry;
   gb::DevBuf<Pair> d_pairs;
   gb::DevBuf<int32_t> d_out4;

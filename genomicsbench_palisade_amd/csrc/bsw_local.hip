@@ -48,6 +48,7 @@
 #include "../../include/gb_bsw.h"
 #include "bsw_local_internal.h"
 #include "gb_common.h"
+#include "gb_common_wave.h"
 
 static_assert(sizeof(gb_bsw_lpair) == 56, "gb_bsw_lpair is 56 bytes (include/gb_bsw.h)");
 static_assert(GB_BSW_LOCAL_MAX_TLEN < (1 << 14), "a list entry keeps its row in 14 bits");
@@ -76,21 +77,6 @@ struct Args {
   int oe_del, e_del, oe_ins, e_ins, max_mat;
   int8_t mat[28];
 };
-
-// wave-wide inclusive max scan (Hillis-Steele in 16-lane rows, then row broadcasts)
-__device__ __forceinline__ int scan_max(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x111, 0xF, 0xF, false));  // row_shr:1
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x112, 0xF, 0xF, false));  // row_shr:2
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x114, 0xF, 0xF, false));  // row_shr:4
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x118, 0xF, 0xF, false));  // row_shr:8
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x142, 0xA, 0xF, false));  // row_bcast:15
-  v = max(v, __builtin_amdgcn_update_dpp(kNegInf, v, 0x143, 0xC, 0xF, false));  // row_bcast:31
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) { return __builtin_amdgcn_readlane(scan_max(v), 63); }
-__device__ __forceinline__ int shr1(int v, int lane0) {
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xF, 0xF, false);  // wave_shr:1
-}
 
 struct Res {
   int gmax, te, qe, score2, te2;
@@ -148,7 +134,7 @@ __device__ __forceinline__ void pass(const Args &A, const int8_t *smat, const ui
 
     // A = max(m, E, 0) per column, and the terms of F's scan: F(i,j) = max(0, max_{k<j} (A_k - oe_ins
     // + e_ins k) - e_ins (j-1)). All terms are at least -32768 and at most 2^15 + 2^23.
-    const int hleft = shr1(H[K - 1], 0);  // H(i-1, lane*K - 1); H(i-1,-1) = 0 (ksw.c:149)
+    const int hleft = gb::wave_shr1(H[K - 1], 0);  // H(i-1, lane*K - 1); H(i-1,-1) = 0 (ksw.c:149)
     int a[K], lpx[K];
     int lp = kNegInf;
 #pragma unroll
@@ -159,7 +145,7 @@ __device__ __forceinline__ void pass(const Args &A, const int8_t *smat, const ui
       lpx[c] = lp;
       lp = max(lp, a[c] - oe_ins + ej[c]);
     }
-    const int lex = shr1(scan_max(lp), kNegInf);
+    const int lex = gb::wave_shr1(gb::scan_max<kNegInf>(lp), kNegInf);
     int hmax = 0;
 #pragma unroll
     for (int c = 0; c < K; ++c) {
@@ -177,7 +163,7 @@ __device__ __forceinline__ void pass(const Args &A, const int8_t *smat, const ui
     // lane's own maximum then passes the same test.
     const int thr = min(minsc, gmax + 1);
     if (__builtin_amdgcn_ballot_w64(hmax >= thr) != 0) {
-      const int imax = wave_max(hmax);
+      const int imax = gb::wave_max<kNegInf>(hmax);
       if (imax >= minsc) {
         bool changed = false;
         if (n_b == 0 || last_r + 1 != i) {
@@ -210,7 +196,7 @@ __device__ __forceinline__ void pass(const Args &A, const int8_t *smat, const ui
     if (Hk[c] == gmax && live[c]) cand = lane * K + c;
   R.gmax = gmax;
   R.te = te;
-  R.qe = -wave_max(-cand);
+  R.qe = -gb::wave_max<kNegInf>(-cand);
 
   // score2, te2 (ksw.c:218-226): the first entry with the largest score among those outside te +- w.
   // Rows rise along the list, so "first" is "smallest row", and one max over score << 14 | ~row finds it.
@@ -225,7 +211,7 @@ __device__ __forceinline__ void pass(const Args &A, const int8_t *smat, const ui
       const int row = (int)(u & kRowMask);
       if (row < low || row > high) best = max(best, (int)((u & ~kRowMask) | (kRowMask - (uint32_t)row)));
     }
-    best = wave_max(best);
+    best = gb::wave_max<kNegInf>(best);
   }
   R.score2 = best < 0 ? -1 : best >> kRowBits;
   R.te2 = best < 0 ? -1 : (int)kRowMask - (best & (int)kRowMask);
@@ -301,38 +287,27 @@ int64_t chunk_pairs() {  // GB_BSW_LOCAL_CHUNK (tests: many chunks from a small 
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kChunkPairs)) : kChunkPairs;
 }
 
-thread_local std::vector<Ws *> g_ws;
-
-Ws *find_ws(int dev) {
-  for (auto *w : g_ws)
-    if (w->device == dev) return w;
-  return nullptr;
-}
-
-int get_ws(int dev, Ws **out) {
-  if ((*out = find_ws(dev))) return GB_OK;
+static int make_ws(int dev, Ws **out) {
   auto *W = new Ws();
   W->device = dev;
   hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = W->stream.create();
   for (auto &ev : W->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = ev.create();
   int st = GB_ERR_HIP;
   if (e == hipSuccess)
     st = W->d_ctl.reserve(4);
   else
     gb::set_error("gb_bsw_local workspace: %s", hipGetErrorString(e));
   if (st) {
-    for (auto &ev : W->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    if (W->stream) (void)hipStreamDestroy(W->stream);
     delete W;
     return st;
   }
-  g_ws.push_back(W);
   *out = W;
   return GB_OK;
 }
+
+int get_ws(int dev, Ws **out) { return gb::thread_ws(dev, out, make_ws); }
 
 int run_resident(Ws *W, const gb_bsw_params *params, int max_mat, const Pair *d_pairs, int64_t m, const uint8_t *d_tgt,
                  const uint8_t *d_qry, int32_t *d_out8, int64_t list_cap, hipEvent_t e0, hipEvent_t e1) {
@@ -418,7 +393,7 @@ int gb_bsw_local_timing(float *kernel_ms) {
   GB_ARG(kernel_ms, "gb_bsw_local_timing: null argument");
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
-  const gbbswl::Ws *W = gbbswl::find_ws(dev);
+  const gbbswl::Ws *W = gb::find_thread_ws<gbbswl::Ws>(dev);
   if (!W) {
     gb::set_error("gb_bsw_local_timing: gb_bsw_local has not run on this thread and device");
     return GB_ERR_STATE;

@@ -19,10 +19,10 @@ struct Pair {  // device descriptor, 32 B
 // entries a pass over tlen rows can append: never on two adjacent rows (ksw.c:193)
 __host__ __device__ inline int64_t list_entries(int tlen) { return (tlen + 1) / 2 + 1; }
 
-struct Ws {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct Ws {  // the calling thread's, through gb::thread_ws
   int device = -1, num_cus = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  gb::Stream stream;
+  gb::Event ev[2];
   gb::DevBuf<uint8_t> d_tgt, d_qry;
   gb::DevBuf<Pair> d_pairs;
   gb::DevBuf<int32_t> d_out8;

@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -32,7 +31,6 @@
 #include <cstring>
 #include <new>
 #include <stdexcept>
-#include <thread>
 #include <vector>
 
 #include "../../include/gb_bsw.h"
@@ -192,40 +190,6 @@ __global__ __launch_bounds__(256) void bsw_matesw_region_kernel(DevArgs A) {
 
 // ---- host bookkeeping -----------------------------------------------------------------------------
 
-int thread_count(const char *who, int *out) {
-  int nth = 16;
-  if (const char *te = getenv("GB_BSW_MATESW_THREADS")) {
-    char *end = nullptr;
-    const long v = strtol(te, &end, 10);
-    GB_ARG(end != te && *end == 0 && v >= 1, "%s: GB_BSW_MATESW_THREADS = \"%s\" is not a thread count", who, te);
-    nth = (int)std::min<long>(v, 64);
-  }
-  *out = std::max(1, std::min(nth, (int)std::max(1u, std::thread::hardware_concurrency())));
-  return GB_OK;
-}
-
-template <class F>
-void parallel(int nth, F body) {  // body(t) for t in [0, nth); an exception in a thread is rethrown here
-  std::atomic<int> failed{0};
-  auto guarded = [&](int t) {
-    try {
-      body(t);
-    } catch (...) {
-      failed.store(1);
-    }
-  };
-  std::vector<std::thread> th;
-  try {
-    for (int t = 1; t < nth; ++t) th.emplace_back(guarded, t);
-  } catch (...) {
-    for (auto &x : th) x.join();
-    throw;
-  }
-  guarded(0);
-  for (auto &x : th) x.join();
-  if (failed.load()) throw std::bad_alloc();
-}
-
 // the orientations anchor a need not try: failed, or the mate already has a region at a proper distance
 inline int skip_mask(const Rescue &C, const Reg &a, const std::vector<Reg> &ma) {
   int skip = 0;
@@ -272,21 +236,22 @@ int rescue_rounds(Rescue &C, Aligner &A) {
   std::vector<Req> req;
   std::vector<Out> out;
   int st = GB_OK, nth0 = 1;
-  if ((st = thread_count(who, &nth0))) return st;
+  if ((st = gb::thread_count(who, "GB_BSW_MATESW_THREADS", &nth0))) return st;
   for (int32_t j = 0; !active.empty(); ++j) {
     const int64_t nt = (int64_t)active.size();
     const int nth = nt < 256 ? 1 : nth0;
     mask.resize((size_t)nt), base.resize((size_t)nt + 1);
     auto anchor_of = [&](int64_t i) -> const Reg & { return C.regs[C.reg_off[i] + anc[(size_t)(anc_off[(size_t)i] + j)]]; };
-    parallel(nth, [&](int t) {
+    st = gb::parallel(who, nth, [&](int t) {
       for (int64_t k = nt * t / nth; k < nt * (t + 1) / nth; ++k)
         mask[(size_t)k] = skip_mask(C, anchor_of(active[(size_t)k]), C.lists[(size_t)(active[(size_t)k] ^ 1)]);
     });
+    if (st) return st;
     base[0] = 0;
     for (int64_t k = 0; k < nt; ++k) base[(size_t)k + 1] = base[(size_t)k] + (4 - __builtin_popcount(mask[(size_t)k]));
     const int64_t nq = base[(size_t)nt];
     req.resize((size_t)nq), out.resize((size_t)nq);
-    parallel(nth, [&](int t) {
+    st = gb::parallel(who, nth, [&](int t) {
       for (int64_t k = nt * t / nth; k < nt * (t + 1) / nth; ++k) {
         const int64_t i = active[(size_t)k];
         const Reg &a = anchor_of(i);
@@ -295,6 +260,7 @@ int rescue_rounds(Rescue &C, Aligner &A) {
           if (!(mask[(size_t)k] >> r & 1)) req[(size_t)at++] = Req{a.rb, a.rid, r, (int32_t)(i ^ 1), 0};
       }
     });
+    if (st) return st;
     lap();
     if (nq) {
       if ((st = A.run(req.data(), nq, out.data()))) return st;
@@ -302,7 +268,7 @@ int rescue_rounds(Rescue &C, Aligner &A) {
       C.requests += nq;
     }
     t0 = Clock::now();
-    parallel(nth, [&](int t) {
+    st = gb::parallel(who, nth, [&](int t) {
       for (int64_t k = nt * t / nth; k < nt * (t + 1) / nth; ++k) {
         const int64_t i = active[(size_t)k];
         const Reg &a = anchor_of(i);
@@ -339,6 +305,7 @@ int rescue_rounds(Rescue &C, Aligner &A) {
         C.n_sw[(size_t)i] += n;
       }
     });
+    if (st) return st;
     // the tasks that have an anchor j + 1
     size_t m = 0;
     for (size_t k = 0; k < active.size(); ++k)
@@ -351,11 +318,11 @@ int rescue_rounds(Rescue &C, Aligner &A) {
 
 // ---- device aligner ---------------------------------------------------------------------------------
 
-inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+using gb::round_up;
 
-struct MWs {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct MWs {  // the calling thread's, through gb::thread_ws
   int device = -1;
-  hipEvent_t ev[6] = {};
+  gb::Event ev[6];
   gb::PinnedBuf<Req> h_req;
   gb::PinnedBuf<Out> h_out;
   gb::PinnedBuf<uint8_t> h_in;
@@ -375,27 +342,23 @@ struct Timing {
   bool valid;
 };
 
-thread_local std::vector<MWs *> g_ws;
 thread_local Timing g_timing = {0.f, 0.f, 0.f, 0.f, 0, 0, false};  // of this thread's last call
 
 int get_ws(int dev, MWs **out) {
-  for (auto *w : g_ws)
-    if (w->device == dev) return *out = w, GB_OK;
-  auto *W = new MWs();
-  W->device = dev;
-  hipError_t e = hipSuccess;
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e != hipSuccess) {
-    gb::set_error("gb_bsw_mate_rescue workspace: %s", hipGetErrorString(e));
+  return gb::thread_ws(dev, out, [](int dev, MWs **out) {
+    auto *W = new MWs();
+    W->device = dev;
+    hipError_t e = hipSuccess;
     for (auto &ev : W->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    delete W;
-    return GB_ERR_HIP;
-  }
-  g_ws.push_back(W);
-  *out = W;
-  return GB_OK;
+      if (e == hipSuccess) e = ev.create();
+    if (e != hipSuccess) {
+      gb::set_error("gb_bsw_mate_rescue workspace: %s", hipGetErrorString(e));
+      delete W;
+      return GB_ERR_HIP;
+    }
+    *out = W;
+    return GB_OK;
+  });
 }
 
 struct DevAligner : Aligner {
@@ -424,13 +387,13 @@ struct DevAligner : Aligner {
     if ((st = gbgc::ensure_device(R, dev))) return st;
     W->fetch_ms = W->dp_ms = W->region_ms = 0.f;
     // one staging block: q_off (8 B per read), l_query (4 B), contig ends, the query bytes
-    const int64_t o_qoff = 0, o_lq = o_qoff + up(n_reads * 8, 16), o_ce = o_lq + up(n_reads * 4, 16);
+    const int64_t o_qoff = 0, o_lq = o_qoff + round_up(n_reads * 8, 16), o_ce = o_lq + round_up(n_reads * 4, 16);
     const int64_t nc = contig_end ? n_contigs : 1;
-    const int64_t o_q = o_ce + up(nc * 8, 16);
+    const int64_t o_q = o_ce + round_up(nc * 8, 16);
     int64_t q_half = 0;
     for (int64_t r = 0; r < n_reads; ++r)
-      if (C->reg_off[(r ^ 1) + 1] > C->reg_off[r ^ 1]) q_half += up(l_query[r], 4);
-    q_half = up(std::max<int64_t>(q_half, 1), 16);
+      if (C->reg_off[(r ^ 1) + 1] > C->reg_off[r ^ 1]) q_half += round_up<int64_t>(l_query[r], 4);
+    q_half = round_up(std::max<int64_t>(q_half, 1), 16);
     const int64_t bytes = o_q + q_half;
     if ((st = W->h_in.reserve((size_t)bytes, (size_t)bytes * 2))) return st;
     if ((st = W->d_in.reserve((size_t)bytes, (size_t)bytes * 2))) return st;
@@ -446,7 +409,7 @@ struct DevAligner : Aligner {
       if (C->reg_off[(r ^ 1) + 1] == C->reg_off[r ^ 1]) continue;  // nobody looks for this read
       hq[r] = qo, hl[r] = l_query[r];
       std::memcpy(h + o_q + qo, qer + idq[r], (size_t)l_query[r]);
-      qo += up(l_query[r], 4);
+      qo += round_up<int64_t>(l_query[r], 4);
     }
     if (contig_end)
       std::memcpy(hc, contig_end, (size_t)nc * 8);
@@ -472,7 +435,7 @@ struct DevAligner : Aligner {
     D.q_off = Rc.q_off;
     D.l_query = Rc.l_query;
     D.rev_base = q_half;
-    D.stride = up(std::max<int64_t>(max_win, 1), 16);
+    D.stride = round_up(std::max<int64_t>(max_win, 1), 16);
     for (int r = 0; r < 4; ++r) D.low[r] = C->pes[r].low, D.high[r] = C->pes[r].high;
     D.min_seed_len = C->opt.min_seed_len;
     D.a = C->opt.a;
@@ -719,7 +682,7 @@ int rescue_impl(const gb_bsw_params *params, const gb_bsw_pe_opt *opt, const str
   }
 
   int nth = 1;
-  if (thread_count(who, &nth)) return GB_ERR_ARG;  // refused here, before any device work
+  if (gb::thread_count(who, "GB_BSW_MATESW_THREADS", &nth)) return GB_ERR_ARG;  // refused here, before any device work
   g_timing = Timing{0.f, 0.f, 0.f, 0.f, 0, 0, true};
   Rescue C;
   C.opt = *opt;

@@ -29,7 +29,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -38,7 +37,6 @@
 #include <functional>
 #include <new>
 #include <stdexcept>
-#include <thread>
 #include <vector>
 
 #include "../../include/gb_bsw.h"
@@ -763,10 +761,10 @@ void host_range(const Plan &P, const uint8_t *is_alt, const int64_t *coords, int
   }
 }
 
-struct MWs {  // one per (calling thread, device), never freed (see gb_bsw_get_scores16_ex)
+struct MWs {  // the calling thread's, through gb::thread_ws
   int device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {};
+  gb::Stream stream;
+  gb::Event ev[4];
   gb::PinnedBuf<uint8_t> h_in;
   gb::DevBuf<uint8_t> d_in;
   gb::DevBuf<Chain> d_ch;
@@ -781,8 +779,6 @@ struct MWs {  // one per (calling thread, device), never freed (see gb_bsw_get_s
   gb::DevBuf<gb_bsw_chain_info> d_info;
 };
 
-thread_local std::vector<MWs *> g_ws;
-
 struct Timing {
   float build_ms, filter_ms, emit_ms;
   int64_t host_reads;
@@ -791,30 +787,21 @@ struct Timing {
 thread_local Timing g_timing = {0.f, 0.f, 0.f, 0, false};
 
 int get_ws(int dev, MWs **out) {
-  for (auto *w : g_ws)
-    if (w->device == dev) {
-      *out = w;
-      return GB_OK;
-    }
-  auto *W = new MWs();
-  W->device = dev;
-  hipError_t e = hipStreamCreateWithFlags(&W->stream, hipStreamNonBlocking);
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e != hipSuccess) {
-    gb::set_error("gb_bsw_seeds2chains workspace: %s", hipGetErrorString(e));
+  return gb::thread_ws(dev, out, [](int dev, MWs **out) {
+    auto *W = new MWs();
+    W->device = dev;
+    hipError_t e = W->stream.create();
     for (auto &ev : W->ev)
-      if (ev) (void)hipEventDestroy(ev);
-    if (W->stream) (void)hipStreamDestroy(W->stream);
-    delete W;
-    return GB_ERR_HIP;
-  }
-  g_ws.push_back(W);
-  *out = W;
-  return GB_OK;
+      if (e == hipSuccess) e = ev.create();
+    if (e != hipSuccess) {
+      gb::set_error("gb_bsw_seeds2chains workspace: %s", hipGetErrorString(e));
+      delete W;
+      return GB_ERR_HIP;
+    }
+    *out = W;
+    return GB_OK;
+  });
 }
-
-inline int64_t up16(int64_t v) { return (std::max<int64_t>(v, 1) + 15) / 16 * 16; }
 
 // The device reads of the call: CSR over all reads (a host read owns no chain here) into the given host
 // arrays, which hold n_reads + 1, n_coords + 1, n_coords and n_coords entries.
@@ -830,7 +817,7 @@ int run_device(const Plan &P, const uint8_t *is_alt, const int64_t *coords, int6
   int64_t size = 0;
   auto take = [&](int64_t bytes) {
     const int64_t at = size;
-    size += up16(bytes);
+    size += gb::round_up<int64_t>(std::max<int64_t>(bytes, 1), 16);
     return at;
   };
   const int64_t o_reads = take(nr * (int64_t)sizeof(ReadItem)), o_mems = take(nm * (int64_t)sizeof(SMem)),
@@ -972,39 +959,15 @@ static int seeds2chains_impl(const gb_bsw_chain_opt *opt, int32_t stage, int64_t
   std::vector<HostOut> H;
   std::vector<int64_t> cut;
   if (P.host_reads) {
-    int nth = 16;
-    if (const char *te = getenv("GB_BSW_MKCHAIN_THREADS")) {
-      char *end = nullptr;
-      const long v = strtol(te, &end, 10);
-      GB_ARG(end != te && *end == 0 && v >= 1, "%s: GB_BSW_MKCHAIN_THREADS = \"%s\" is not a thread count", who, te);
-      nth = (int)std::min<long>(v, 64);
-    }
-    nth = std::max(1, std::min(nth, (int)std::max(1u, std::thread::hardware_concurrency())));
+    int nth = 1;
+    if ((st = gb::thread_count(who, "GB_BSW_MKCHAIN_THREADS", &nth))) return st;
     if (P.host_reads < 256) nth = 1;
     H.resize((size_t)nth);
     for (int t = 0; t <= nth; ++t) cut.push_back(n_reads * t / nth);
-    // nothing may leave a thread, and a thread that cannot start must not leave the others unjoined
-    std::atomic<int> failed{0};
-    auto body = [&](int t) {
-      try {
-        host_range(P, is_alt, coords, cut[(size_t)t], cut[(size_t)t + 1], &H[(size_t)t]);
-      } catch (...) {
-        failed.store(1);
-      }
-    };
-    std::vector<std::thread> th;
-    try {
-      for (int t = 1; t < nth; ++t) th.emplace_back(body, t);
-    } catch (...) {
-      for (auto &x : th) x.join();
-      throw;
-    }
-    body(0);
-    for (auto &x : th) x.join();
-    if (failed.load()) {
-      gb::set_error("%s: out of host memory on the host path", who);
-      return GB_ERR_NOMEM;
-    }
+    if ((st = gb::parallel(who, nth, [&](int t) {
+           host_range(P, is_alt, coords, cut[(size_t)t], cut[(size_t)t + 1], &H[(size_t)t]);
+         })))
+      return st;
   }
   const bool any_dev = P.host_reads < n_reads;
   // with both paths in one call the device's CSR is spliced with the host reads' afterwards

@@ -31,7 +31,6 @@
 #include <new>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/gb_bsw.h"
@@ -253,59 +252,36 @@ int run_host(Call &C, gb_ref *R) {
          "%s: the call reads the reference's host copy, which was released at the reference's first device use",
          C.who);
   const uint8_t *pac = R->host.data();
-  int nth = 16;
-  if (const char *te = getenv("GB_BSW_REGS_THREADS")) {
-    char *end = nullptr;
-    const long v = strtol(te, &end, 10);
-    GB_ARG(end != te && *end == 0 && v >= 1, "%s: GB_BSW_REGS_THREADS = \"%s\" is not a thread count", C.who, te);
-    nth = (int)std::min<long>(v, 64);
-  }
-  nth = std::max(1, std::min(nth, (int)std::max(1u, std::thread::hardware_concurrency())));
+  int nth = 1;
+  if (const int st = gb::thread_count(C.who, "GB_BSW_REGS_THREADS", &nth)) return st;
   if (C.n_reads < 256) nth = 1;
   std::vector<int32_t> zall((size_t)std::max<int64_t>(C.n_regs, 1));
-  std::atomic<int> failed{0};
   std::atomic<int64_t> bad_read{-1};
-  auto body = [&](int t) {
-    try {
-      HostDp W;
-      for (int64_t r = C.n_reads * t / nth; r < C.n_reads * (t + 1) / nth; ++r) {
-        const int64_t off = C.reg_off[r];
-        State &st = C.state[(size_t)r];
-        std::memset(&st, 0, sizeof(st));
-        st.n = st.n_out = (int32_t)(C.reg_off[r + 1] - off);
-        Request rq{};
-        bool have = false;
-        int score = 0;
-        for (;;) {
-          dedup_read(C.opt, C.is_alt, C.work.data() + off, st, have, score, C.idq[r], &rq);
-          if (!st.waiting) break;
-          if (rq.re - rq.rb > GB_BSW_GLOBAL_MAX_TLEN) {
-            int64_t none = -1;
-            bad_read.compare_exchange_strong(none, r);
-            return;
-          }
-          score = host_dp(C.dp, pac, R->l_pac, C.qer, rq, W);
-          have = true;
+  const int pst = gb::parallel(C.who, nth, [&](int t) {
+    HostDp W;
+    for (int64_t r = C.n_reads * t / nth; r < C.n_reads * (t + 1) / nth; ++r) {
+      const int64_t off = C.reg_off[r];
+      State &st = C.state[(size_t)r];
+      std::memset(&st, 0, sizeof(st));
+      st.n = st.n_out = (int32_t)(C.reg_off[r + 1] - off);
+      Request rq{};
+      bool have = false;
+      int score = 0;
+      for (;;) {
+        dedup_read(C.opt, C.is_alt, C.work.data() + off, st, have, score, C.idq[r], &rq);
+        if (!st.waiting) break;
+        if (rq.re - rq.rb > GB_BSW_GLOBAL_MAX_TLEN) {
+          int64_t none = -1;
+          bad_read.compare_exchange_strong(none, r);
+          return;
         }
-        if (C.stage) mark_read(C.opt, st.n_out, C.work.data() + off, zall.data() + off, C.opt.id0 + r);
+        score = host_dp(C.dp, pac, R->l_pac, C.qer, rq, W);
+        have = true;
       }
-    } catch (...) {
-      failed.store(1);
+      if (C.stage) mark_read(C.opt, st.n_out, C.work.data() + off, zall.data() + off, C.opt.id0 + r);
     }
-  };
-  std::vector<std::thread> th;
-  try {
-    for (int t = 1; t < nth; ++t) th.emplace_back(body, t);
-  } catch (...) {
-    for (auto &x : th) x.join();
-    throw;
-  }
-  body(0);
-  for (auto &x : th) x.join();
-  if (failed.load()) {
-    gb::set_error("%s: out of host memory on the host path", C.who);
-    return GB_ERR_NOMEM;
-  }
+  });
+  if (pst) return pst;
   GB_ARG(bad_read.load() < 0, "%s: read %lld needs a merge alignment over more than %d reference bases", C.who,
          (long long)bad_read.load(), GB_BSW_GLOBAL_MAX_TLEN);
   g_timing.host_reads = C.n_reads;

@@ -182,8 +182,8 @@ __global__ __launch_bounds__(128) void chain_kernel(Args A) {
         __hip_atomic_store(&sl.seq, i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
       cons_v = __hip_atomic_load(&consumed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      wx = dpp_shr_u64(wx, xi);
-      wy = dpp_shr_u64(wy, yi);
+      wx = gb::wave_shr1(wx, xi);
+      wy = gb::wave_shr1(wy, yi);
     }
     {  // slot n: no candidates (the consumer precomputes one anchor ahead and reads it last)
       while (n - lds_count(&consumed) >= kSlots) __builtin_amdgcn_s_sleep(1);
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(128) void chain_kernel(Args A) {
       pB = pq;
     } else {
       const int32_t mx = scan_max(lane == 0 ? INT_MIN : psc);
-      pB = max(dpp_shr_i32(mx, INT_MIN), pq);
+      pB = max(gb::wave_shr1(mx, INT_MIN), pq);
     }
     ppj = wp1;
     // "targets[j] == a" from the parents of lanes >= 1: a stamp a+1 at each parent (a parent is an
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(128) void chain_kernel(Args A) {
       take(i + 1, pst, pq, sgn);
       // From here to the walk's result the code is one basic block: the next anchor's preparation
       // (independent of this anchor's result) and this anchor's resolution interleave.
-      const int32_t ws1 = dpp_shr_i32(ws, 0), wp1 = dpp_shr_i32(wpar, -1);
+      const int32_t ws1 = gb::wave_shr1(ws, 0), wp1 = gb::wave_shr1(wpar, -1);
       prepare_math(i + 1, sgn, ws1, wp1);
       // ---- anchor i: no candidate passes the filters when jtop < st (okm == 0) ----------------
       const int32_t jtop = i - 1;
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(128) void chain_kernel(Args A) {
       const int32_t pki = (PROF >= 1 && (A.exp & 64)) ? M : (J >= 0 && pkJ > M) ? pkJ : M;
       ws = lane == 0 ? M : ws1;
       wpar = lane == 0 ? J : wp1;
-      wpk = dpp_shr_i32(wpk, pki);
+      wpk = gb::wave_shr1(wpk, pki);
       Mprev = M;
       Jprev = J;
       if (pc) c_tail += __builtin_amdgcn_s_memtime() - t2;
@@ -710,21 +710,14 @@ int gb_chain_batch_destroy(gb_chain_batch *B) {
 int gb_chain(int64_t ncalls, const int64_t *offsets, const float *avg_qspan, const int32_t *params4,
              const uint64_t *x, const uint64_t *y, int32_t *scores, int32_t *parents, int32_t *targets,
              int32_t *peak_scores) {
-  // one cached batch per (host thread, device): repeated host_chain_kernel calls reuse its stream,
-  // events and grow-only buffers. Never freed (freeing at thread exit could run after the HIP
-  // runtime is torn down).
+  // the calling thread's cached batch on this device: repeated host_chain_kernel calls reuse its
+  // stream, events and grow-only buffers
   int st = validate(ncalls, offsets, avg_qspan, params4, x, y);
   if (st) return st;
-  thread_local std::vector<std::pair<int, gb_chain_batch *>> ws;
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
   gb_chain_batch *B = nullptr;
-  for (auto &w : ws)
-    if (w.first == dev) B = w.second;
-  if (!B) {
-    if ((st = batch_new(&B))) return st;
-    ws.emplace_back(dev, B);
-  }
+  if ((st = gb::thread_ws(dev, &B, [](int, gb_chain_batch **out) { return batch_new(out); }))) return st;
   const bool hp = getenv("GB_CHAIN_HOSTPROF") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   if ((st = batch_fill(B, ncalls, offsets, avg_qspan, params4, x, y))) return st;

@@ -6,6 +6,8 @@
 #include <climits>
 #include <cstdint>
 
+#include "gb_common_wave.h"
+
 namespace gbchain {
 
 constexpr int kRing = 8192;      // stamp ring >= max_iter (5000) + 64 candidates: any window
@@ -15,34 +17,9 @@ constexpr int kMaxSkip = 25;    // host_kernel.cpp:42
 
 __device__ __forceinline__ int ilog2_32(uint32_t v) { return 31 - __clz((int)v); }  // v > 0 (LogTable256)
 
-__device__ __forceinline__ int dpp_shr_i32(int v, int lane0) {
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xF, 0xF, false);  // wave_shr:1
-}
-__device__ __forceinline__ uint64_t dpp_shr_u64(uint64_t v, uint64_t lane0) {
-  const int lo = dpp_shr_i32((int)(uint32_t)v, (int)(uint32_t)lane0);
-  const int hi = dpp_shr_i32((int)(uint32_t)(v >> 32), (int)(uint32_t)(lane0 >> 32));
-  return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-
-// wave-wide inclusive scans with DPP (row_shr 1/2/4/8 inside 16-lane rows, then row_bcast 15/31)
-__device__ __forceinline__ int32_t scan_max(int32_t v) {
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x111, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x112, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x114, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x118, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x142, 0xA, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x143, 0xC, 0xF, false));
-  return v;
-}
-__device__ __forceinline__ int32_t scan_min(int32_t v) {
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x111, 0xF, 0xF, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x112, 0xF, 0xF, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x114, 0xF, 0xF, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x118, 0xF, 0xF, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x142, 0xA, 0xF, false));
-  v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x143, 0xC, 0xF, false));
-  return v;
-}
+// the wave-wide scans of gb_common_wave.h with the identities of the chain kernels
+__device__ __forceinline__ int32_t scan_max(int32_t v) { return gb::scan_max<INT_MIN>(v); }
+__device__ __forceinline__ int32_t scan_min(int32_t v) { return gb::scan_min<INT_MAX>(v); }
 __device__ __forceinline__ int32_t load_l2(const int32_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_load sc1 (bypasses L1)
 }
@@ -99,7 +76,7 @@ __device__ __forceinline__ bool resolve_step(int32_t sc, bool ok, int32_t pj, in
   S[(ok & (pj >= st)) ? (pj & (RING - 1)) : RING + lane] = stamp;
   const bool tgt = S[(jtop - lane) & (RING - 1)] == stamp;
   const int32_t mx = scan_max(sc);  // inclusive max scan
-  const int32_t before = max(dpp_shr_i32(mx, INT_MIN), M);
+  const int32_t before = max(gb::wave_shr1(mx, INT_MIN), M);
   const bool upd = sc > before;  // false on filtered lanes: before >= M >= 0 > INT_MIN
   const bool plus = ok & !upd & tgt;
   const uint64_t um_all = __builtin_amdgcn_ballot_w64(upd), pm = __builtin_amdgcn_ballot_w64(plus);

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(64) void chain_rows(RowArgs A) {
         const int32_t sc = ok ? (int32_t)((uint32_t)sg + (uint32_t)fj) : INT_MIN;
         const int32_t mx = hmax(sc);
         const int32_t Mh = hi ? M1 : M0, Nh = hi ? N1 : N0;
-        const int32_t sh = dpp_shr_i32(mx, INT_MIN);
+        const int32_t sh = gb::wave_shr1(mx, INT_MIN);
         const int32_t before = hl == 0 ? Mh : max(sh, Mh);
         const bool upd = sc > before;
         const bool plus = ok & !upd & tgt;
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(64) void chain_rows(RowArgs A) {
         const int32_t sc = ok ? (int32_t)((uint32_t)sg + (uint32_t)fj) : INT_MIN;
         const int32_t mx = hmax(sc);
         const int32_t Mh = hi ? M1 : M0, Nh = hi ? N1 : N0;
-        const int32_t sh = dpp_shr_i32(mx, INT_MIN);
+        const int32_t sh = gb::wave_shr1(mx, INT_MIN);
         const int32_t before = hl == 0 ? Mh : max(sh, Mh);
         const bool upd = sc > before;
         const bool plus = ok & !upd & tgt;

@@ -259,7 +259,7 @@ __device__ __forceinline__ bool resolve_tagged(int32_t sc, bool ok, int32_t pj, 
   const int32_t j = jtop - lane;
   const bool tg = S[j & (RING - 1)] == ring_tag<RING>(k, j);
   const int32_t mx = scan_max(sc);
-  const int32_t before = max(dpp_shr_i32(mx, INT_MIN), M);
+  const int32_t before = max(gb::wave_shr1(mx, INT_MIN), M);
   const bool upd = sc > before;
   const bool plus = ok & !upd & tg;
   const uint64_t um_all = __builtin_amdgcn_ballot_w64(upd), pm = __builtin_amdgcn_ballot_w64(plus);
@@ -359,10 +359,10 @@ __device__ __forceinline__ void verify_chunk(SplitArgs A, const uint64_t *need, 
       const bool clash = __builtin_amdgcn_ballot_w64(conflict) != 0;
       if (CHECK && (M != fi || J != pi || clash) && first_bad == INT_MAX) first_bad = i;
     }
-    wx = dpp_shr_u64(wx, xi);
-    wy = dpp_shr_u64(wy, yi);
-    wf = dpp_shr_i32(wf, fi);
-    wp = dpp_shr_i32(wp, pi);
+    wx = gb::wave_shr1(wx, xi);
+    wy = gb::wave_shr1(wy, yi);
+    wf = gb::wave_shr1(wf, fi);
+    wp = gb::wave_shr1(wp, pi);
   }
   if (lane == 0) {
     if (CHECK && first_bad != INT_MAX) atomicMin(A.fail + ch.sc, first_bad);
@@ -687,57 +687,55 @@ int split_plan(gb_chain_batch *B, const int64_t *offsets, const uint64_t *x, con
   {
     const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(),
                                                                  offsets[ncalls] / 200000 + 1}));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++)
-      th.emplace_back([&, t] {
-        for (int64_t c = t; c < ncalls; c += nt) {
-          const int32_t n = (int32_t)(offsets[c + 1] - offsets[c]);
-          const bool maybe = seg >= 64 && (target > 0 ? (int64_t)n > std::min<int64_t>(target, 2 * (int64_t)seg)
-                                                      : (int64_t)n >= 2 * (int64_t)seg);
-          if (!maybe) {
-            walk(c, nullptr);
-            continue;
-          }
-          Cand &K = cand[(size_t)c];
-          K.st.resize((size_t)n);
-          walk(c, K.st.data());
-          if (!sorted[(size_t)c]) {
+    const int st = gb::parallel("gb_chain_batch_create", nt, [&](int t) {
+      for (int64_t c = t; c < ncalls; c += nt) {
+        const int32_t n = (int32_t)(offsets[c + 1] - offsets[c]);
+        const bool maybe = seg >= 64 && (target > 0 ? (int64_t)n > std::min<int64_t>(target, 2 * (int64_t)seg)
+                                                    : (int64_t)n >= 2 * (int64_t)seg);
+        if (!maybe) {
+          walk(c, nullptr);
+          continue;
+        }
+        Cand &K = cand[(size_t)c];
+        K.st.resize((size_t)n);
+        walk(c, K.st.data());
+        if (!sorted[(size_t)c]) {
+          K.st = std::vector<int32_t>();
+          continue;
+        }
+        // with a row target: a call's segments are as long as its window leaves room for under the
+        // target (block = warm-up + capped window + segment), and a call no longer than the target
+        // runs whole
+        int32_t segc = seg;
+        if (target > 0) {
+          if (n <= target) {
             K.st = std::vector<int32_t>();
             continue;
           }
-          // with a row target: a call's segments are as long as its window leaves room for under the
-          // target (block = warm-up + capped window + segment), and a call no longer than the target
-          // runs whole
-          int32_t segc = seg;
-          if (target > 0) {
-            if (n <= target) {
-              K.st = std::vector<int32_t>();
-              continue;
-            }
-            const int32_t cw = std::min(maxwin[(size_t)c], wcap);
-            segc = std::max(seg_floor, std::min(seg, target - cw - warm));
-          }
-          // equal segments of at most segc anchors: the longest block of the launch (a segment, its
-          // window and its warm-up) is then bounded by segc, not by a last segment of up to 2 segc - 1
-          const int32_t nseg = (n + segc - 1) / segc, L = (n + nseg - 1) / nseg;
-          K.L = L;
-          K.as.resize((size_t)nseg);
-          K.win.resize((size_t)nseg);
-          for (int32_t k = 0; k < nseg; k++) {
-            const int32_t cs = k * L, es = k + 1 == nseg ? n : (k + 1) * L;
-            // trunc: the warm-up starts `warm` anchors before c_s whatever the window (the first
-            // anchors' spec loops then miss their oldest candidates, which only matters -- and is
-            // then caught by the verification -- for loops that would have reached them)
-            const int32_t a =
-                k == 0 ? 0 : std::max(0, trunc ? cs - warm : std::max(K.st[(size_t)cs], cs - wcap) - warm);
-            int32_t w = 0;
-            for (int32_t i = a; i < es; i++) w = std::max(w, i - std::max(a, K.st[(size_t)i]));
-            K.as[(size_t)k] = a;
-            K.win[(size_t)k] = w;
-          }
+          const int32_t cw = std::min(maxwin[(size_t)c], wcap);
+          segc = std::max(seg_floor, std::min(seg, target - cw - warm));
         }
-      });
-    for (auto &t : th) t.join();
+        // equal segments of at most segc anchors: the longest block of the launch (a segment, its
+        // window and its warm-up) is then bounded by segc, not by a last segment of up to 2 segc - 1
+        const int32_t nseg = (n + segc - 1) / segc, L = (n + nseg - 1) / nseg;
+        K.L = L;
+        K.as.resize((size_t)nseg);
+        K.win.resize((size_t)nseg);
+        for (int32_t k = 0; k < nseg; k++) {
+          const int32_t cs = k * L, es = k + 1 == nseg ? n : (k + 1) * L;
+          // trunc: the warm-up starts `warm` anchors before c_s whatever the window (the first
+          // anchors' spec loops then miss their oldest candidates, which only matters -- and is
+          // then caught by the verification -- for loops that would have reached them)
+          const int32_t a =
+              k == 0 ? 0 : std::max(0, trunc ? cs - warm : std::max(K.st[(size_t)cs], cs - wcap) - warm);
+          int32_t w = 0;
+          for (int32_t i = a; i < es; i++) w = std::max(w, i - std::max(a, K.st[(size_t)i]));
+          K.as[(size_t)k] = a;
+          K.win[(size_t)k] = w;
+        }
+      }
+    });
+    if (st) return st;
   }
   auto vpush = [&](int64_t in, int64_t out, int32_t n, int64_t c, int32_t mode, int32_t win) {
     const int32_t cls = (rows_on && mono[(size_t)c]) ? 2 : (win <= kRingSmall ? 1 : 0);

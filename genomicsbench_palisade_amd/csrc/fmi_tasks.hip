@@ -383,7 +383,7 @@ __global__ __launch_bounds__(64) void fmi_task_wave(TaskArgs A) {
 
 // Per host thread and device: stream, grow-only device buffers and a pinned staging buffer (the
 // reference's methods are called from OpenMP threads sharing one FMI_search object).
-struct Workspace {  // never deleted (workspace())
+struct Workspace {  // the calling thread's, through gb::thread_ws
   int device = -1;
   hipStream_t stream = nullptr;
   gb::DevBuf<uint8_t> buf[10];
@@ -400,21 +400,21 @@ struct Workspace {  // never deleted (workspace())
 };
 
 Workspace &workspace(int device) {
-  static thread_local std::vector<Workspace *> ws;
-  if ((int)ws.size() <= device) ws.resize(device + 1, nullptr);
-  if (!ws[device]) {
-    ws[device] = new Workspace();
-    ws[device]->device = device;
-  }
-  return *ws[device];
+  Workspace *W = nullptr;
+  (void)gb::thread_ws(device, &W, [](int dev, Workspace **out) {
+    *out = new Workspace();
+    (*out)->device = dev;
+    return GB_OK;
+  });
+  return *W;
 }
+
+using gb::round_up;
 
 struct HostTasks {
   std::vector<int32_t> rid, intv;
   std::vector<int16_t> qpos;
 };
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The checks of one call's tasks (the reads they name, their lengths and query positions); the
 // extent of enc_qdb they read and their longest read.
@@ -473,7 +473,7 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
 
   // the reads, once per call: [qdb extent | lens | offs]
   {
-    const size_t o_lens = up256((size_t)extent), o_offs = o_lens + up256(4 * (size_t)nrid),
+    const size_t o_lens = round_up((size_t)extent, 256), o_offs = o_lens + round_up(4 * (size_t)nrid, 256),
                  bytes = o_offs + 4 * (size_t)nrid;
     if (int st = W.ensure(0, bytes)) return st;
     if (int st = W.ensure_host(bytes)) return st;
@@ -504,11 +504,12 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
   for (int pass = 0; pass < 2 && !todo.empty(); pass++) {
     const int32_t n = (int32_t)todo.size();
     // task inputs (uploaded): [cursor 8 B | rid n | intv n | qpos n]
-    const size_t i_rid = 256, i_intv = i_rid + up256(4 * (size_t)n), i_qpos = i_intv + up256(4 * (size_t)n),
+    const size_t i_rid = 256, i_intv = i_rid + round_up(4 * (size_t)n, 256),
+                 i_qpos = i_intv + round_up(4 * (size_t)n, 256),
                  in_bytes = i_qpos + 2 * (size_t)n;
     // control words (downloaded): [counts n | rounds n | tcalls n | toff n | next_pos n]
-    const size_t c_rounds = up256(4 * (size_t)n), c_tcalls = c_rounds + up256(4 * (size_t)n),
-                 c_toff = c_tcalls + up256(4 * (size_t)n), c_np = c_toff + up256(4 * (size_t)n),
+    const size_t c_rounds = round_up(4 * (size_t)n, 256), c_tcalls = c_rounds + round_up(4 * (size_t)n, 256),
+                 c_toff = c_tcalls + round_up(4 * (size_t)n, 256), c_np = c_toff + round_up(4 * (size_t)n, 256),
                  ctl_bytes = c_np + 2 * (size_t)n;
     const size_t rec_bytes = sizeof(TSmem) * (size_t)n * cap;
     int st = W.ensure(3, in_bytes);
@@ -516,7 +517,7 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
     if (!st) st = W.ensure(7, ctl_bytes);
     if (!st) st = W.ensure(8, sizeof(TEnt) * (size_t)n * (maxlen + 2));
     if (!st) st = W.ensure(9, rec_bytes);
-    if (!st) st = W.ensure_host(std::max(std::max(in_bytes, up256(ctl_bytes) + 256), rec_bytes));
+    if (!st) st = W.ensure_host(std::max(std::max(in_bytes, round_up(ctl_bytes, 256) + 256), rec_bytes));
     if (st) return st;
     uint8_t *h = W.h;
     std::memset(h, 0, 8);
@@ -570,9 +571,9 @@ int run_tasks(gb_fmi_index *idx, int mode, const uint8_t *qdb, const int32_t *le
     // the control words and the packed count (the input block's first word) in one download each
     GB_HIP(hipMemcpyAsync(h, dctl, ctl_bytes, hipMemcpyDeviceToHost, s));
     unsigned long long packed = 0;
-    GB_HIP(hipMemcpyAsync(h + up256(ctl_bytes), din, 8, hipMemcpyDeviceToHost, s));
+    GB_HIP(hipMemcpyAsync(h + round_up(ctl_bytes, 256), din, 8, hipMemcpyDeviceToHost, s));
     GB_HIP(hipStreamSynchronize(s));
-    std::memcpy(&packed, h + up256(ctl_bytes), 8);
+    std::memcpy(&packed, h + round_up(ctl_bytes, 256), 8);
     GB_ARG(packed <= (unsigned long long)n * cap, "FMI_search: %llu packed records exceed the %lld slots", packed,
            (long long)n * cap);
     const int32_t *hc = reinterpret_cast<const int32_t *>(h);

@@ -15,6 +15,18 @@ void set_error(const char *fmt, ...) {
   g_err = buf;
 }
 const char *last_error() { return g_err.c_str(); }
+
+int thread_count(const char *who, const char *env_name, int *n) {
+  int nth = 16;
+  if (const char *te = getenv(env_name)) {
+    char *end = nullptr;
+    const long v = strtol(te, &end, 10);
+    GB_ARG(end != te && *end == 0 && v >= 1, "%s: %s = \"%s\" is not a thread count", who, env_name, te);
+    nth = (int)std::min<long>(v, 64);
+  }
+  *n = std::max(1, std::min(nth, (int)std::max(1u, std::thread::hardware_concurrency())));
+  return GB_OK;
+}
 }  // namespace gb
 
 extern "C" {

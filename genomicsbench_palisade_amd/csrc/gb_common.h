@@ -1,10 +1,15 @@
-// gb_common.h -- shared host-side plumbing for the C ABI (error state, HIP checks).
+// gb_common.h -- shared host-side plumbing for the C ABI: error state, HIP checks, owning buffers and
+// handles, per-thread workspaces, host fork-join.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <thread>
+#include <type_traits>
+#include <vector>
 
 #include "../../include/gb.h"
 
@@ -111,6 +116,118 @@ template <typename T>
 using DevBuf = Buf<T, DeviceMem>;
 template <typename T>
 using PinnedBuf = Buf<T, PinnedMem>;
+
+// Owning stream and event handles: move-only, null exactly when not created, destroyed with the
+// object, and converting to the raw handle. create() returns HIP's status, so the caller words its
+// own error. The storage-duration rule of the buffers above holds for them too.
+template <typename H, hipError_t (*Destroy)(H)>
+class Handle {
+ public:
+  Handle() = default;
+  ~Handle() { reset(); }
+  Handle(const Handle &) = delete;
+  Handle &operator=(const Handle &) = delete;
+  Handle(Handle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  Handle &operator=(Handle &&o) noexcept {
+    if (this != &o) {
+      reset();
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+  void reset() {
+    if (h_) (void)Destroy(h_);
+    h_ = nullptr;
+  }
+  operator H() const { return h_; }
+
+ protected:
+  H h_ = nullptr;
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {  // a non-blocking stream
+  hipError_t create() {
+    reset();
+    return hipStreamCreateWithFlags(&h_, hipStreamNonBlocking);
+  }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+  hipError_t create() {
+    reset();
+    return hipEventCreate(&h_);
+  }
+};
+
+// The calling thread's workspace of type T for (device, slot): make(dev, &T*) builds it on first use
+// and it is registered only when make returns GB_OK, so a failed make is tried again by the next
+// call. One workspace per (calling thread, device, slot), never freed: a free at thread exit could
+// run after the HIP runtime is torn down. The registry is keyed by T alone and holds raw pointers
+// only; the workspace itself lives on the heap, so the storage-duration rule above holds.
+template <typename T>
+struct ThreadWs {
+  int dev, slot;
+  T *ws;
+  static std::vector<ThreadWs> &all() {
+    thread_local std::vector<ThreadWs> v;
+    return v;
+  }
+};
+template <typename T>
+T *find_thread_ws(int dev, int slot = 0) {  // null before the first successful make
+  for (const auto &e : ThreadWs<T>::all())
+    if (e.dev == dev && e.slot == slot) return e.ws;
+  return nullptr;
+}
+template <typename T, typename Make>
+int thread_ws(int dev, int slot, T **out, Make &&make) {
+  if ((*out = find_thread_ws<T>(dev, slot))) return GB_OK;
+  if (const int st = make(dev, out)) return *out = nullptr, st;
+  ThreadWs<T>::all().push_back({dev, slot, *out});
+  return GB_OK;
+}
+template <typename T, typename Make>
+int thread_ws(int dev, T **out, Make &&make) {
+  return thread_ws<T>(dev, 0, out, make);
+}
+
+// Host worker threads for a call: the count in the environment variable env_name (default 16, values
+// above 64 taken as 64), then at most the hardware's. Anything but a count >= 1 is GB_ERR_ARG.
+int thread_count(const char *who, const char *env_name, int *n);
+
+// Fork-join: body(t) for t in [0, nth), t == 0 on the caller. Everything that started is joined
+// and no exception leaves: a body that threw, or a thread that could not start, is GB_ERR_NOMEM.
+template <typename F>
+int parallel(const char *who, int nth, F &&body) {
+  std::atomic<bool> failed{false};
+  auto guarded = [&](int t) {
+    try {
+      body(t);
+    } catch (...) {
+      failed.store(true);
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    try {
+      for (int t = 1; t < nth; ++t) th.emplace_back(guarded, t);
+    } catch (...) {
+      failed.store(true);
+    }
+    guarded(0);
+    for (auto &x : th) x.join();
+  }
+  if (failed.load()) {
+    set_error("%s: out of host memory on the host path", who);
+    return GB_ERR_NOMEM;
+  }
+  return GB_OK;
+}
+
+// v rounded up to a multiple of a (v >= 0, a > 0); the type is v's
+template <typename T>
+constexpr T round_up(T v, std::common_type_t<T> a) {
+  return (v + a - 1) / a * a;
+}
 
 // roctx range around a host entry point (visible in rocprofv3 --marker-trace; a no-op otherwise)
 struct Range {

@@ -40,6 +40,7 @@
 
 #include "../../include/gb_phmm.h"
 #include "gb_common.h"
+#include "gb_common_wave.h"
 
 namespace {
 
@@ -197,10 +198,6 @@ struct __attribute__((aligned(2 * sizeof(T)))) Brec {
   T z, w;
 };
 
-__device__ __forceinline__ int dpp_shr(int v, int lane0) {
-  // wave_shr:1 (DPP ctrl 0x138); lane 0 has no source lane and keeps `lane0` (bound_ctrl off).
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xF, 0xF, false);
-}
 template <int (*F)(int, int)>
 __device__ __forceinline__ float dpp(float v, float keep) {
   return __builtin_bit_cast(float, F(__builtin_bit_cast(int, v), __builtin_bit_cast(int, keep)));
@@ -273,8 +270,8 @@ struct LaneState {
 template <typename T, bool kSum, bool kWrite>
 __device__ __forceinline__ void phmm_step(const Brec<T> &rec, uint32_t h, LaneState<T> &st,
                                           const RowParams<T> &P, T &sumM, T &sumX, Brec<T> *wr, bool last_lane) {
-  const T X = dpp<dpp_shr>(st.wo, rec.w);          // X[r][c]
-  const T zdn = dpp<dpp_shr>(st.zo, rec.z);        // bracket for column c+1
+  const T X = dpp<gb::wave_shr1>(st.wo, rec.w);          // X[r][c]
+  const T zdn = dpp<gb::wave_shr1>(st.zo, rec.z);        // bracket for column c+1
   const T dist = select_dist(P.rmask, h, P.dmatch, P.dmis);
   const T M = st.zd * dist;
   const T Y = st.Mp * P.pMY + st.Yp * P.pYY;
@@ -404,16 +401,6 @@ struct __attribute__((aligned(16))) StackEnt {
   int R;
   uint32_t read_off, out_idx;
 };
-
-__device__ __forceinline__ int scan_add(int v) {  // wave-wide inclusive prefix sum (DPP)
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Rolled stripes. A 64-row stripe costs C + 63 wave steps for 64 x C cells: the anti-diagonal fill.
@@ -680,7 +667,7 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
   if (!am) return 0;
   const int na = __builtin_popcountll(am);
   const int rows = act ? (int)(d.dims & 0xffff) + 2 : 0;
-  const int incl = scan_add(rows);
+  const int incl = gb::scan_add(rows);
   const int T_rows = __builtin_amdgcn_readlane(incl, 63);
   // compaction: entry a = the a-th computed testcase (lane order), gathered into lane a
   int src = 0;
@@ -921,8 +908,8 @@ __device__ __forceinline__ void phmm_step2(const Brec<T> &rec, uint32_t h, uint3
                                            T &sMa, T &sXa, T &sMb, T &sXb, Brec<T> *wr, bool last_lane) {
   const T Xb = A.wo;
   const T zdnb = A.zo;
-  const T Xa = dpp<dpp_shr>(B.wo, rec.w);
-  const T zdna = dpp<dpp_shr>(B.zo, rec.z);
+  const T Xa = dpp<gb::wave_shr1>(B.wo, rec.w);
+  const T zdna = dpp<gb::wave_shr1>(B.zo, rec.z);
   const T Mb = B.zd * select_dist(PB.rmask, hb, PB.dmatch, PB.dmis);
   const T Ma = A.zd * select_dist(PA.rmask, h, PA.dmatch, PA.dmis);
   const T Yb = B.Mp * PB.pMY + B.Yp * PB.pYY;
@@ -1031,7 +1018,7 @@ __device__ __forceinline__ void phmm_stack2(const Stack &S, const uint32_t *__re
   TcDesc d = {0, 0, 0, 0};
   if (lane < na) d = descs[stk_tc[S.first + lane]];
   const int rows = lane < na ? (int)(d.dims & 0xffff) + 2 : 0;
-  const int incl = scan_add(rows);
+  const int incl = gb::scan_add(rows);
   const int T_rows = __builtin_amdgcn_readlane(incl, 63);
   const int e_start = incl - rows, e_R = rows - 2;  // entry a in lane a
   const T init_Y = tab.init_const / (T)C;
@@ -1411,7 +1398,7 @@ struct HostClock {
 // the old one, and hipFree waits for the device.
 int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
   const size_t nn = std::max(n, 1);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  auto up = [](size_t x) { return gb::round_up<size_t>(x, 256); };
   const size_t sz[8] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
                         up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
                         up(sizeof(Stack) * nn),  // at most one stack per testcase
@@ -1484,7 +1471,7 @@ void host_reserve(gb_phmm_batch *b, size_t n, size_t pool_bytes, int threads) {
 struct StageLayout {
   size_t o_tc, o_stk, o_pool, total;
   StageLayout(size_t n, size_t pool_bytes) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    auto up = [](size_t x) { return gb::round_up<size_t>(x, 256); };
     o_tc = up(sizeof(TcDesc) * n);
     o_stk = o_tc + up(sizeof(uint32_t) * n);
     o_pool = o_stk + up(sizeof(Stack) * n);
@@ -1620,20 +1607,13 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     ch[t].pool = &b->pools[t];
     ch[t].pool->clear();
   }
-  if (nth == 1) {
-    pack_chunk(ch[0]);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; t++) th.emplace_back(pack_chunk, std::ref(ch[t]));
-    pack_chunk(ch[0]);
-    for (auto &x : th) x.join();
-  }
+  if (int st = gb::parallel("gb_phmm_batch_create", nth, [&](int t) { pack_chunk(ch[t]); })) return st;
   clk.mark("pack");
   // merge: chunk pool bases, global haplotype ids (first appearance), one pool in the staging buffer
   std::vector<size_t> base(nth + 1, 0);
   for (int t = 0; t < nth; t++) base[t + 1] = base[t] + ch[t].pool->size();
   GB_ARG(base[nth] < (1ull << 32), "batch pool exceeds 4 GiB");
-  const size_t pool_bytes = std::max<size_t>((base[nth] + 15) & ~size_t(15), 16);
+  const size_t pool_bytes = std::max<size_t>(gb::round_up<size_t>(base[nth], 16), 16);
   const StageLayout L(nn, pool_bytes);
   if (int st = stage_reserve(b, L.total, sizeof(TcDesc) * nn)) return st;
   desc = (TcDesc *)b->h_stage.get();
@@ -1664,14 +1644,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
       desc[k].hap_off = hap_off_of[hid[k]];
     }
   };
-  if (nth == 1) {
-    merge_chunk(0);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nth; t++) th.emplace_back(merge_chunk, t);
-    merge_chunk(0);
-    for (auto &x : th) x.join();
-  }
+  if (int st = gb::parallel("gb_phmm_batch_create", nth, merge_chunk)) return st;
   std::memset(h_pool + base[nth], 0, pool_bytes - base[nth]);
   clk.mark("merge");
   // Stacks (phmm_stack): testcases grouped by haplotype, stacked up to kStackRows rows (R + 2 per
@@ -1844,8 +1817,8 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   if (n_long) {
     // records + codes of one long stack per workgroup of the persistent kLong grid
     b->long_grid = std::min(n_long, b->f64_grid);
-    b->scratch_stride = (sizeof(Brec<double>) * (size_t)(max_h_long + kBndPad + kRecPad) +
-                         (size_t)(max_h_long + kBndPad + kWave) + 16 + 255) & ~(size_t)255;
+    b->scratch_stride = gb::round_up<size_t>(sizeof(Brec<double>) * (size_t)(max_h_long + kBndPad + kRecPad) +
+                                                 (size_t)(max_h_long + kBndPad + kWave) + 16, 256);
     const size_t need = b->scratch_stride * (size_t)b->long_grid;
     if (int st = b->d_scratch.reserve(need)) return st;
   }
@@ -1889,19 +1862,12 @@ int batch_new(DeviceTables *tabs, gb_phmm_batch **out) {
   return GB_OK;
 }
 
-// gb_phmm_compute's workspace: one batch per (host thread, device), refilled on every call so the
-// reference's once-per-batch computelikelihoodsboth does not create streams, events and buffers
-// each time. Kept for the life of the thread's process (never freed: freeing at thread exit could
-// run after the HIP runtime is torn down).
+// gb_phmm_compute's workspaces: the calling thread's batch for (device, slot), refilled on every call
+// so the reference's once-per-batch computelikelihoodsboth does not create streams, events and
+// buffers each time.
 gb_phmm_batch *thread_workspace(DeviceTables *tabs, int *st, int slot = 0) {
-  thread_local std::unordered_map<int, std::vector<gb_phmm_batch *>> ws;
-  auto &v = ws[tabs->device];
-  if ((int)v.size() <= slot) v.resize(slot + 1, nullptr);
-  if (v[slot]) return v[slot];
   gb_phmm_batch *b = nullptr;
-  *st = batch_new(tabs, &b);
-  if (*st) return nullptr;
-  v[slot] = b;
+  *st = gb::thread_ws(tabs->device, slot, &b, [tabs](int, gb_phmm_batch **out) { return batch_new(tabs, out); });
   return b;
 }
 
@@ -2152,7 +2118,7 @@ int gb_phmm_batch_results(gb_phmm_batch *b, double *results, float *raw_f, doubl
   std::vector<double> rd_v;
   const float *rf;
   const double *rd;
-  const size_t off_d = (sizeof(float) * (size_t)n + 255) & ~(size_t)255;
+  const size_t off_d = gb::round_up<size_t>(sizeof(float) * (size_t)n, 256);
   if (b->h_stage && b->h_stage.capacity() >= off_d + sizeof(double) * (size_t)n) {
     GB_HIP(hipMemcpyAsync(b->h_stage, b->d_rf, sizeof(float) * n, hipMemcpyDeviceToHost, b->stream));
     GB_HIP(hipMemcpyAsync(b->h_stage + off_d, b->d_rd, sizeof(double) * n, hipMemcpyDeviceToHost, b->stream));
@@ -2181,14 +2147,8 @@ int gb_phmm_batch_results(gb_phmm_batch *b, double *results, float *raw_f, doubl
   };
   // the host log10 epilogue (bit-exact, unlike the device one) over a few threads for big jobs
   const int nt = n >= (1 << 16) ? (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-  if (nt == 1) {
-    part(0, n);
-  } else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; t++) th.emplace_back(part, (int)((int64_t)n * t / nt), (int)((int64_t)n * (t + 1) / nt));
-    for (auto &t : th) t.join();
-  }
-  return GB_OK;
+  return gb::parallel("gb_phmm_batch_results", nt,
+                      [&](int t) { part((int)((int64_t)n * t / nt), (int)((int64_t)n * (t + 1) / nt)); });
 }
 
 int gb_phmm_batch_timing(gb_phmm_batch *b, float *f32_ms, float *f64_ms, float *total_ms) {
