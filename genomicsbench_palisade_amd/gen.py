@@ -395,3 +395,115 @@ def bsw_dataset(num_pairs: int = BSW_LARGE_PAIRS, seed: int = 11, threads: int =
     with ThreadPoolExecutor(max(1, threads)) as ex:
         parts = list(ex.map(lambda a: bsw_pairs(a[1], seed=[seed, a[0]]), enumerate(sizes)))
     return concat_bsw(parts) if parts else bsw_pairs(0, seed)
+
+
+# ---- abea: adaptive banded event alignment (benchmarks/abea) ----
+
+ABEA_K = 6
+
+
+class AbeaReads:
+    """Reads for abea.align: `model` is float32 [4096, 3] (level_mean, level_stdv, level_log_stdv by k-mer
+    rank), `seqs` the concatenated ASCII bases (uint8), `events` the concatenated event means (float32); read
+    r is seqs[seq_off[r]:][:seq_len[r]] and events[event_off[r]:][:n_events[r]] with scale[r], shift[r]."""
+
+    def __init__(self, model, seqs, events, seq_len, n_events, scale, shift):
+        self.model = np.ascontiguousarray(model, np.float32).reshape(4096, 3)
+        self.seqs = np.ascontiguousarray(seqs, np.uint8)
+        self.events = np.ascontiguousarray(events, np.float32)
+        self.seq_len = np.asarray(seq_len, np.int32)
+        self.n_events = np.asarray(n_events, np.int32)
+        self.scale = np.asarray(scale, np.float32)
+        self.shift = np.asarray(shift, np.float32)
+        self.seq_off = np.concatenate([[0], np.cumsum(self.seq_len[:-1], dtype=np.int64)]).astype(np.int64)[:len(self.seq_len)]
+        self.event_off = np.concatenate([[0], np.cumsum(self.n_events[:-1], dtype=np.int64)]).astype(np.int64)[:len(self.seq_len)]
+
+    @property
+    def n(self):
+        return len(self.seq_len)
+
+    def pair_cap(self):
+        """n_events + n_kmers over the reads: always enough for the pairs."""
+        return int(self.n_events.sum(dtype=np.int64) + (self.seq_len.astype(np.int64) - ABEA_K + 1).sum())
+
+    def read(self, r):
+        """(bases, event means) of read r."""
+        return (self.seqs[self.seq_off[r]:self.seq_off[r] + self.seq_len[r]],
+                self.events[self.event_off[r]:self.event_off[r] + self.n_events[r]])
+
+    def subset(self, idx):
+        idx = list(idx)
+        rs = [self.read(r) for r in idx]
+        return AbeaReads(self.model, np.concatenate([s for s, _ in rs]) if rs else np.zeros(0, np.uint8),
+                         np.concatenate([e for _, e in rs]) if rs else np.zeros(0, np.float32),
+                         self.seq_len[idx], self.n_events[idx], self.scale[idx], self.shift[idx])
+
+
+def abea_model(rng, grid=None):
+    """A pore model shaped like r9.4 (levels 55..130 pA, stdv 1..3.5). With `grid`, levels are multiples of
+    it and every stdv is 2, so that equal scores are common."""
+    m = np.zeros((4096, 3), np.float32)
+    if grid:
+        m[:, 0] = (np.round(rng.uniform(55, 130, 4096) / grid) * grid).astype(np.float32)
+        m[:, 1] = 2.0
+    else:
+        m[:, 0] = rng.uniform(55, 130, 4096).astype(np.float32)
+        m[:, 1] = rng.uniform(1.0, 3.5, 4096).astype(np.float32)
+    m[:, 2] = np.log(m[:, 1].astype(np.float64)).astype(np.float32)
+    return m
+
+
+def abea_kmer_ranks(bases):
+    """Rank of every k-mer of an ASCII sequence; a base other than ACGT counts as A (align.c:10-38)."""
+    code = np.zeros(256, np.int64)
+    code[ord("C")], code[ord("G")], code[ord("T")] = 1, 2, 3
+    c = code[np.asarray(bases, np.uint8)]
+    n = len(c) - ABEA_K + 1
+    r = np.zeros(n, np.int64)
+    for i in range(ABEA_K):
+        r = r * 4 + c[i:i + n]
+    return r
+
+
+def abea_read(rng, model, seq_len, events_per_kmer=1.6, noise=0.7, missing=0.0, scale=1.0, shift=0.0, non_acgt=0.0,
+              skip_lead=0, skip_run=0, poly_a=0, quantum=0.125):
+    """One synthetic read: random bases, then for every k-mer a number of events (mean events_per_kmer; none
+    with probability `missing` for inner k-mers, none for the first `skip_lead` k-mers and for a run of
+    `skip_run` in the middle; with `poly_a` the middle holds that many AAAAAA k-mers in a row and only the first
+    has events), each the k-mer's scaled level plus `noise` stdv of Gaussian noise, rounded to
+    a multiple of `quantum`. Returns (bases uint8, event means float32)."""
+    bases = BASES[rng.integers(0, 4, seq_len)].copy()
+    if non_acgt:
+        bases[rng.random(seq_len) < non_acgt] = ord("N")
+    nk = seq_len - ABEA_K + 1
+    if poly_a:
+        bases[nk // 2:nk // 2 + poly_a + ABEA_K - 1] = ord("A")
+    ranks = abea_kmer_ranks(bases)
+    if events_per_kmer >= 1:
+        cnt = 1 + rng.poisson(events_per_kmer - 1, nk)
+    else:
+        cnt = (rng.random(nk) < events_per_kmer).astype(np.int64)
+    drop = rng.random(nk) < missing
+    drop[:1], drop[-1:] = False, False
+    cnt[drop] = 0
+    cnt[:skip_lead] = 0
+    if skip_run:
+        cnt[nk // 2:nk // 2 + skip_run] = 0
+    if poly_a:
+        cnt[nk // 2 + 1:nk // 2 + poly_a] = 0
+    if cnt.sum() == 0:
+        cnt[-1] = 1
+    k = np.repeat(np.arange(nk), cnt)
+    lv = np.float32(scale) * model[ranks[k], 0] + np.float32(shift)
+    ev = lv + noise * model[ranks[k], 1] * rng.standard_normal(len(k))
+    ev = (np.round(ev / quantum) * quantum).astype(np.float32)
+    return bases, ev
+
+
+def abea_set(rng, n, lo=500, hi=10000, model=None, events_per_kmer=1.6, noise=0.7, missing=0.01):
+    """n reads with seq_len log-uniform in lo..hi over one model."""
+    model = abea_model(rng) if model is None else model
+    lens = np.exp(rng.uniform(np.log(lo), np.log(hi), n)).astype(np.int64)
+    rs = [abea_read(rng, model, int(l), events_per_kmer, noise, missing) for l in lens]
+    return AbeaReads(model, np.concatenate([b for b, _ in rs]), np.concatenate([e for _, e in rs]),
+                     [len(b) for b, _ in rs], [len(e) for _, e in rs], np.ones(n, np.float32), np.zeros(n, np.float32))
