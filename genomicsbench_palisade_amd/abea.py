@@ -2,6 +2,9 @@
 align() (benchmarks/abea/src/align.c:169-548), executed by csrc/bsw_abea.hip.
 
 Reads are gen.AbeaReads (one model, concatenated ASCII bases and event means, per-read lengths and scalings).
+
+Below it, the mirror of gb_abea_hmm_score (include/gb_bsw_abea_hmm.h): the methylation profile-HMM scores, the
+batch form of profile_hmm_score (src/hmm.c:620-727), executed by csrc/bsw_abea_hmm.hip over gen.AbeaHmmItems.
 """
 from __future__ import annotations
 
@@ -10,6 +13,7 @@ import ctypes
 import numpy as np
 
 from . import GbError, check, lib
+from .gen import ABEA_HMM_ITEM_DTYPE, ABEA_HMM_READ_DTYPE
 
 K = 6
 BANDWIDTH = 100
@@ -89,4 +93,64 @@ def plan():
     return a.value, b.value, c.value
 
 
-__all__ = ["GbError", "align", "align_raw", "plan", "read_records", "timing"]
+# ---- gb_abea_hmm_score (include/gb_bsw_abea_hmm.h): methylation profile-HMM scores, csrc/bsw_abea_hmm.hip ----
+
+HMM_MODEL_SIZE = 15625
+HMM_MAX_KMERS = 256
+HMM_MAX_EVENTS = 65536
+HMM_LOGSUM_TBL = 16000
+HMM_READ_DTYPE = ABEA_HMM_READ_DTYPE
+HMM_ITEM_DTYPE = ABEA_HMM_ITEM_DTYPE
+
+
+def _hmm_decl():
+    L = lib()
+    if getattr(L, "_abea_hmm_decl", False):
+        return L
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    L.gb_abea_hmm_score.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.gb_abea_hmm_timing.argtypes = [vp, vp]
+    L.gb_abea_hmm_logsum_table.argtypes = [vp]
+    L._abea_hmm_decl = True
+    return L
+
+
+def hmm_score_raw(model, seqs, events, reads, items, scores=None):
+    """gb_abea_hmm_score as it is: (status, scores). No exception. `scores` is the buffer the call writes (a new
+    one of NaN by default), so that a refusal can be seen to leave it untouched."""
+    L = _hmm_decl()
+    model = np.ascontiguousarray(model, np.float32)
+    seqs = np.ascontiguousarray(seqs, np.uint8)
+    events = np.ascontiguousarray(events, np.float32)
+    reads = np.ascontiguousarray(reads, HMM_READ_DTYPE)
+    items = np.ascontiguousarray(items, HMM_ITEM_DTYPE)
+    if scores is None:
+        scores = np.full(len(items), np.nan, np.float32)
+    st = L.gb_abea_hmm_score(_buf(model), _buf(seqs), len(seqs), _buf(events), len(events), _buf(reads), len(reads),
+                             _buf(items), len(items), _buf(scores))
+    return st, scores
+
+
+def hmm_score(x):
+    """profile_hmm_score of every item of a gen.AbeaHmmItems: float32 [n], bit for bit the reference's."""
+    st, scores = hmm_score_raw(x.model, x.seqs, x.events, x.reads, x.items)
+    check(st, "gb_abea_hmm_score")
+    return scores
+
+
+def hmm_timing():
+    """(kernel ms, cells) of this thread's last device call of hmm_score."""
+    ms, c = ctypes.c_float(), ctypes.c_int64()
+    check(_hmm_decl().gb_abea_hmm_timing(ctypes.addressof(ms), ctypes.addressof(c)), "gb_abea_hmm_timing")
+    return ms.value, c.value
+
+
+def hmm_logsum_table():
+    """The 16 000 entries of the p7_FLogsum table the library built."""
+    t = np.zeros(HMM_LOGSUM_TBL, np.float32)
+    check(_hmm_decl().gb_abea_hmm_logsum_table(t.ctypes.data), "gb_abea_hmm_logsum_table")
+    return t
+
+
+__all__ = ["GbError", "align", "align_raw", "hmm_logsum_table", "hmm_score", "hmm_score_raw", "hmm_timing", "plan",
+           "read_records", "timing"]

@@ -507,3 +507,172 @@ def abea_set(rng, n, lo=500, hi=10000, model=None, events_per_kmer=1.6, noise=0.
     rs = [abea_read(rng, model, int(l), events_per_kmer, noise, missing) for l in lens]
     return AbeaReads(model, np.concatenate([b for b, _ in rs]), np.concatenate([e for _, e in rs]),
                      [len(b) for b, _ in rs], [len(e) for _, e in rs], np.ones(n, np.float32), np.zeros(n, np.float32))
+
+
+# ---- abea: methylation profile-HMM scores (benchmarks/abea, profile_hmm_score) ----
+
+ABEA_HMM_MODEL_SIZE = 15625
+ABEA_HMM_READ_DTYPE = np.dtype([("event_off", "<i8"), ("n_events", "<i4"), ("scale", "<f4"), ("shift", "<f4"),
+                                ("var", "<f4"), ("log_var", "<f4"), ("pad", "<i4"), ("events_per_base", "<f8")])
+ABEA_HMM_ITEM_DTYPE = np.dtype([("seq_off", "<i8"), ("seq_len", "<i4"), ("read", "<i4"), ("event_start", "<i4"),
+                                ("event_stop", "<i4"), ("rc", "u1"), ("flags", "u1"), ("pad", "u1", (2,)), ("tail", "<i4")])  # tail: the C struct's padding to 8 bytes
+assert ABEA_HMM_READ_DTYPE.itemsize == 40 and ABEA_HMM_ITEM_DTYPE.itemsize == 32
+
+
+class AbeaHmmItems:
+    """Items for abea.hmm_score: `model` is float32 [15625, 3] by k-mer rank over ACGMT, `seqs` the concatenated
+    ASCII strings, `events` the concatenated event means, `reads` ABEA_HMM_READ_DTYPE records and `items`
+    ABEA_HMM_ITEM_DTYPE records (include/gb_bsw_abea_hmm.h)."""
+
+    def __init__(self, model, seqs, events, reads, items):
+        self.model = np.ascontiguousarray(model, np.float32).reshape(ABEA_HMM_MODEL_SIZE, 3)
+        self.seqs = np.ascontiguousarray(seqs, np.uint8)
+        self.events = np.ascontiguousarray(events, np.float32)
+        self.reads = np.ascontiguousarray(reads, ABEA_HMM_READ_DTYPE)
+        self.items = np.ascontiguousarray(items, ABEA_HMM_ITEM_DTYPE)
+
+    @property
+    def n(self):
+        return len(self.items)
+
+    @property
+    def n_kmers(self):
+        return self.items["seq_len"].astype(np.int64) - ABEA_K + 1
+
+    @property
+    def n_rows(self):
+        return np.abs(self.items["event_stop"].astype(np.int64) - self.items["event_start"]) + 1
+
+    def cells(self):
+        return int((self.n_kmers * self.n_rows).sum())
+
+    def subset(self, idx):
+        """The same buffers and reads with items[idx]."""
+        return AbeaHmmItems(self.model, self.seqs, self.events, self.reads, self.items[np.asarray(idx, np.int64)])
+
+    @staticmethod
+    def concat(parts, model=None):
+        """The items of several sets over one model (the first part's unless given), offsets and read indices
+        shifted."""
+        reads, items = [], []
+        seq_pos = ev_pos = n_reads = 0
+        for p in parts:
+            rd, it = p.reads.copy(), p.items.copy()
+            rd["event_off"] += ev_pos
+            it["seq_off"] += seq_pos
+            it["read"] += n_reads
+            reads.append(rd)
+            items.append(it)
+            seq_pos, ev_pos, n_reads = seq_pos + len(p.seqs), ev_pos + len(p.events), n_reads + len(p.reads)
+        return AbeaHmmItems(parts[0].model if model is None else model, np.concatenate([p.seqs for p in parts]),
+                            np.concatenate([p.events for p in parts]), np.concatenate(reads), np.concatenate(items))
+
+    def item(self, i):
+        """(string, the read's event means, read record, item record) of item i."""
+        it = self.items[i]
+        rd = self.reads[it["read"]]
+        return (self.seqs[it["seq_off"]:it["seq_off"] + it["seq_len"]],
+                self.events[rd["event_off"]:rd["event_off"] + rd["n_events"]], rd, it)
+
+
+def abea_cpg_model(rng, grid=None):
+    """A seeded pore model over ACGMT shaped like abea_model (levels 55..130 pA, stdv 1..3.5). With `grid`, levels
+    are multiples of it and every stdv is 2."""
+    m = np.zeros((ABEA_HMM_MODEL_SIZE, 3), np.float32)
+    if grid:
+        m[:, 0] = (np.round(rng.uniform(55, 130, len(m)) / grid) * grid).astype(np.float32)
+        m[:, 1] = 2.0
+    else:
+        m[:, 0] = rng.uniform(55, 130, len(m)).astype(np.float32)
+        m[:, 1] = rng.uniform(1.0, 3.5, len(m)).astype(np.float32)
+    m[:, 2] = np.log(m[:, 1].astype(np.float64)).astype(np.float32)
+    return m
+
+
+def abea_hmm_kmer_ranks(strings, rc):
+    """Ranks [..., n_kmers] of the k-mers of ASCII strings [..., len] in the order profile_hmm_score visits
+    them: k-mer ki starts at ki for rc == 0 and at len - ki - 6 for rc == 1 (rc is a scalar or one value per
+    string); base 5 with A C G M T = 0..4 and any other byte 0 (hmm.c:21-52, 382-393)."""
+    code = np.zeros(256, np.int64)
+    for i, ch in enumerate(b"ACGMT"):
+        code[ch] = i
+    c = code[np.asarray(strings, np.uint8)]
+    n = c.shape[-1] - ABEA_K + 1
+    r = np.zeros(c.shape[:-1] + (n,), np.int64)
+    for i in range(ABEA_K):
+        r = r * 5 + c[..., i:i + n]
+    return np.where(np.asarray(rc)[..., None].astype(bool), r[..., ::-1], r)
+
+
+def abea_hmm_items(rng, shapes, model=None, rc=None, flags=3, meth="pair", noise=0.7, cpg=0.08, non_acgmt=0.0,
+                   outliers=0, quantum=None, scale=(0.95, 1.05), shift=(-4.0, 4.0), var=(0.9, 1.2), epb=(1.1, 3.0),
+                   lead=2):
+    """Synthetic site groups for abea.hmm_score. `shapes` is a list of (count, n_kmers, n_rows): `count` reads,
+    each with one CG-bearing string of n_kmers + 5 bases (CG planted with probability `cpg` per position and
+    always in the middle), on the strand `rc` (0, 1, or None for a random one per read), and n_rows events
+    drawn from the levels of the string's k-mers in the order the strand visits them (row r from k-mer
+    r * n_kmers // n_rows, `noise` stdv of Gaussian noise; `outliers` rows per read lie 40 stdv off), between
+    `lead` other events on either side. `meth`: "pair" gives two items per read, the string and its methylated
+    copy (CG turned into MG) over the same events; "none" and "only" give one of them. scale, shift, var and
+    epb are a value or a (lo, hi) range per read; with `quantum` events are rounded to its multiples. `flags`
+    is a value or a list to draw from."""
+    model = abea_cpg_model(rng) if model is None else model
+    C, G, M, N = (ord(x) for x in "CGMN")
+
+    def draw(v, n):
+        return rng.uniform(v[0], v[1], n) if isinstance(v, tuple) else np.full(n, float(v))
+
+    seqs, events, reads, items = [], [], [], []
+    seq_pos = ev_pos = n_reads = 0
+    for count, nk, rows in shapes:
+        L = nk + ABEA_K - 1
+        b = BASES[rng.integers(0, 4, (count, L))].copy()
+        cg = rng.random((count, L - 1)) < cpg
+        cg[:, (L - 1) // 2] = True
+        ii = np.nonzero(cg)
+        b[ii[0], ii[1]] = C
+        b[ii[0], ii[1] + 1] = G
+        if non_acgmt:
+            b[rng.random(b.shape) < non_acgmt] = N
+        m = b.copy()
+        m[:, :-1][(b[:, :-1] == C) & (b[:, 1:] == G)] = M
+        strand = rng.integers(0, 2, count) if rc is None else np.full(count, int(rc))
+        ranks = abea_hmm_kmer_ranks(b, strand)
+        lv = model[ranks[:, (np.arange(rows) * nk) // rows]]  # [count, rows, 3]
+        sc, sh, vr = (draw(v, count).astype(np.float32) for v in (scale, shift, var))
+        ev = (sc[:, None] * lv[..., 0] + sh[:, None]
+              + noise * lv[..., 1] * vr[:, None] * rng.standard_normal((count, rows)))
+        for _ in range(outliers):
+            at = rng.integers(0, rows, count)
+            ev[np.arange(count), at] += 40.0 * lv[np.arange(count), at, 1] * vr
+        n_ev = rows + 2 * lead
+        arr = rng.uniform(60, 120, (count, n_ev))
+        first = np.where(strand == 1, lead + rows - 1, lead)  # row 1's event
+        pos = first[:, None] + np.where(strand == 1, -1, 1)[:, None] * np.arange(rows)[None, :]
+        arr[np.arange(count)[:, None], pos] = ev
+        if quantum:
+            arr = np.round(arr / quantum) * quantum
+        rd = np.zeros(count, ABEA_HMM_READ_DTYPE)
+        rd["event_off"] = ev_pos + n_ev * np.arange(count, dtype=np.int64)
+        rd["n_events"] = n_ev
+        rd["scale"], rd["shift"], rd["var"] = sc, sh, vr
+        rd["log_var"] = np.log(vr.astype(np.float64)).astype(np.float32)
+        rd["events_per_base"] = draw(epb, count)
+        strings = {"pair": (b, m), "none": (b,), "only": (m,)}[meth]
+        it = np.zeros((count, len(strings)), ABEA_HMM_ITEM_DTYPE)
+        it["seq_off"] = seq_pos + L * (len(strings) * np.arange(count, dtype=np.int64)[:, None] + np.arange(len(strings)))
+        it["seq_len"] = L
+        it["read"] = (n_reads + np.arange(count))[:, None]
+        it["event_start"] = first[:, None]
+        it["event_stop"] = (first + np.where(strand == 1, -1, 1) * (rows - 1))[:, None]
+        it["rc"] = strand[:, None]
+        it["flags"] = (rng.choice(np.asarray(flags), count) if np.ndim(flags) else np.full(count, flags))[:, None]
+        seqs.append(np.stack(strings, 1).reshape(-1))
+        events.append(arr.astype(np.float32).reshape(-1))
+        reads.append(rd)
+        items.append(it.reshape(-1))
+        seq_pos += L * len(strings) * count
+        ev_pos += n_ev * count
+        n_reads += count
+    return AbeaHmmItems(model, np.concatenate(seqs), np.concatenate(events), np.concatenate(reads),
+                        np.concatenate(items))
