@@ -17,7 +17,8 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize abea-sanitize abea-hmm-sanitize
+.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize abea-sanitize abea-hmm-sanitize \
+        abea-viterbi-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -28,7 +29,7 @@ $(LIB)/obj/chain_rows.o $(LIB)/obj/phmm.o: HIPFLAGS += -mllvm -amdgpu-sched-stra
 
 # abea's emission divides in f32 and the result is part of the bit-exact contract: ask for the correctly
 # rounded division by name instead of relying on the compiler's default
-$(LIB)/obj/bsw_abea.o $(LIB)/obj/bsw_abea_hmm.o: HIPFLAGS += -fhip-fp32-correctly-rounded-divide-sqrt
+$(LIB)/obj/bsw_abea.o $(LIB)/obj/bsw_abea_hmm.o $(LIB)/obj/bsw_abea_viterbi.o: HIPFLAGS += -fhip-fp32-correctly-rounded-divide-sqrt
 
 # the Makefile itself is a prerequisite: flag changes (the per-object scheduler flags above) rebuild
 $(LIB)/obj/%.o: $(CSRC)/%.hip $(HDRS) Makefile
@@ -149,6 +150,15 @@ tests/_build/abea_hmm_host_check: tests/cpp/abea_hmm_host_check.cpp $(CSRC)/bsw_
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_abea_hmm.hip \
+	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the same for the host path of gb_abea_hmm_align (GB_ABEA_HOST=1). Not part of `all`.
+abea-viterbi-sanitize: tests/_build/abea_viterbi_host_check
+	tests/_build/abea_viterbi_host_check
+tests/_build/abea_viterbi_host_check: tests/cpp/abea_viterbi_host_check.cpp $(CSRC)/bsw_abea_viterbi.hip $(CSRC)/gb_common.cpp $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_abea_viterbi.hip \
 	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:

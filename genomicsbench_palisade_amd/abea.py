@@ -5,6 +5,10 @@ Reads are gen.AbeaReads (one model, concatenated ASCII bases and event means, pe
 
 Below it, the mirror of gb_abea_hmm_score (include/gb_bsw_abea_hmm.h): the methylation profile-HMM scores, the
 batch form of profile_hmm_score (src/hmm.c:620-727), executed by csrc/bsw_abea_hmm.hip over gen.AbeaHmmItems.
+
+Last, the mirror of gb_abea_hmm_align (include/gb_bsw_abea_viterbi.h): Viterbi event alignment with traceback, the
+batch form of profile_hmm_align (src/eventalign.c:703-911), executed by csrc/bsw_abea_viterbi.hip over
+gen.AbeaAlignItems.
 """
 from __future__ import annotations
 
@@ -152,5 +156,76 @@ def hmm_logsum_table():
     return t
 
 
-__all__ = ["GbError", "align", "align_raw", "hmm_logsum_table", "hmm_score", "hmm_score_raw", "hmm_timing", "plan",
+# ---- gb_abea_hmm_align (include/gb_bsw_abea_viterbi.h): Viterbi alignment with traceback, csrc/bsw_abea_viterbi.hip ----
+
+HMM_ALIGN_MODEL_SIZE = 4096
+HMM_PATH_DTYPE = np.dtype([("event_idx", "<i4"), ("kmer_idx", "<i4"), ("l_fm", "<f4"), ("state", "S1"), ("pad", "u1", (3,))])
+assert HMM_PATH_DTYPE.itemsize == 16
+
+
+def _hmm_align_decl():
+    L = lib()
+    if getattr(L, "_abea_hmm_align_decl", False):
+        return L
+    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    L.gb_abea_hmm_align.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]
+    L.gb_abea_hmm_align_timing.argtypes = [vp, vp, vp]
+    L.gb_abea_hmm_align_plan.argtypes = [vp, vp]
+    L._abea_hmm_align_decl = True
+    return L
+
+
+def hmm_align_need(items):
+    """The path_cap the call asks for: rows + k-mers - 1 summed over HMM_ITEM_DTYPE records."""
+    items = np.asarray(items, HMM_ITEM_DTYPE)
+    rows = np.abs(items["event_stop"].astype(np.int64) - items["event_start"]) + 1
+    return int((rows + items["seq_len"].astype(np.int64) - K).sum())
+
+
+def hmm_align_raw(model, seqs, events, reads, items, path_cap=None, path=None, path_off=None):
+    """gb_abea_hmm_align as it is: (status, path buffer, path_off, path_used). No exception. `path` and
+    `path_off` are the buffers the call writes (new ones by default, path_off of -1), so that a refusal can be
+    seen to leave them untouched; path_used starts as -1."""
+    L = _hmm_align_decl()
+    model = np.ascontiguousarray(model, np.float32)
+    seqs = np.ascontiguousarray(seqs, np.uint8)
+    events = np.ascontiguousarray(events, np.float32)
+    reads = np.ascontiguousarray(reads, HMM_READ_DTYPE)
+    items = np.ascontiguousarray(items, HMM_ITEM_DTYPE)
+    cap = hmm_align_need(items) if path_cap is None else int(path_cap)
+    if path is None:
+        path = np.zeros(max(cap, 0), HMM_PATH_DTYPE)
+    if path_off is None:
+        path_off = np.full(len(items) + 1, -1, np.int64)
+    used = ctypes.c_int64(-1)
+    st = L.gb_abea_hmm_align(_buf(model), _buf(seqs), len(seqs), _buf(events), len(events), _buf(reads), len(reads),
+                             _buf(items), len(items), _buf(path), cap, path_off.ctypes.data, ctypes.addressof(used))
+    return st, path, path_off, used.value
+
+
+def hmm_align(x):
+    """profile_hmm_align of every item of a gen.AbeaAlignItems: (records, path_off). Item i owns
+    records[path_off[i]:path_off[i + 1]], HMM_PATH_DTYPE, in the reference's final order and bit for bit its."""
+    st, path, off, used = hmm_align_raw(x.model, x.seqs, x.events, x.reads, x.items)
+    check(st, "gb_abea_hmm_align")
+    return path[:used], off
+
+
+def hmm_align_timing():
+    """(fill ms, walk ms, cells) of this thread's last device call of hmm_align."""
+    f, w, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_int64()
+    check(_hmm_align_decl().gb_abea_hmm_align_timing(ctypes.addressof(f), ctypes.addressof(w), ctypes.addressof(c)),
+          "gb_abea_hmm_align_timing")
+    return f.value, w.value, c.value
+
+
+def hmm_align_plan():
+    """(chunks, largest chunk's workspace bytes) of this thread's last device call of hmm_align."""
+    a, b = ctypes.c_int64(), ctypes.c_int64()
+    check(_hmm_align_decl().gb_abea_hmm_align_plan(ctypes.addressof(a), ctypes.addressof(b)), "gb_abea_hmm_align_plan")
+    return a.value, b.value
+
+
+__all__ = ["GbError", "HMM_PATH_DTYPE", "align", "align_raw", "hmm_align", "hmm_align_need", "hmm_align_plan",
+           "hmm_align_raw", "hmm_align_timing", "hmm_logsum_table", "hmm_score", "hmm_score_raw", "hmm_timing", "plan",
            "read_records", "timing"]

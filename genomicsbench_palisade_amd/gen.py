@@ -524,8 +524,10 @@ class AbeaHmmItems:
     ASCII strings, `events` the concatenated event means, `reads` ABEA_HMM_READ_DTYPE records and `items`
     ABEA_HMM_ITEM_DTYPE records (include/gb_bsw_abea_hmm.h)."""
 
+    MODEL_SIZE = ABEA_HMM_MODEL_SIZE
+
     def __init__(self, model, seqs, events, reads, items):
-        self.model = np.ascontiguousarray(model, np.float32).reshape(ABEA_HMM_MODEL_SIZE, 3)
+        self.model = np.ascontiguousarray(model, np.float32).reshape(self.MODEL_SIZE, 3)
         self.seqs = np.ascontiguousarray(seqs, np.uint8)
         self.events = np.ascontiguousarray(events, np.float32)
         self.reads = np.ascontiguousarray(reads, ABEA_HMM_READ_DTYPE)
@@ -548,10 +550,10 @@ class AbeaHmmItems:
 
     def subset(self, idx):
         """The same buffers and reads with items[idx]."""
-        return AbeaHmmItems(self.model, self.seqs, self.events, self.reads, self.items[np.asarray(idx, np.int64)])
+        return type(self)(self.model, self.seqs, self.events, self.reads, self.items[np.asarray(idx, np.int64)])
 
-    @staticmethod
-    def concat(parts, model=None):
+    @classmethod
+    def concat(cls, parts, model=None):
         """The items of several sets over one model (the first part's unless given), offsets and read indices
         shifted."""
         reads, items = [], []
@@ -564,8 +566,8 @@ class AbeaHmmItems:
             reads.append(rd)
             items.append(it)
             seq_pos, ev_pos, n_reads = seq_pos + len(p.seqs), ev_pos + len(p.events), n_reads + len(p.reads)
-        return AbeaHmmItems(parts[0].model if model is None else model, np.concatenate([p.seqs for p in parts]),
-                            np.concatenate([p.events for p in parts]), np.concatenate(reads), np.concatenate(items))
+        return cls(parts[0].model if model is None else model, np.concatenate([p.seqs for p in parts]),
+                   np.concatenate([p.events for p in parts]), np.concatenate(reads), np.concatenate(items))
 
     def item(self, i):
         """(string, the read's event means, read record, item record) of item i."""
@@ -676,3 +678,99 @@ def abea_hmm_items(rng, shapes, model=None, rc=None, flags=3, meth="pair", noise
         n_reads += count
     return AbeaHmmItems(model, np.concatenate(seqs), np.concatenate(events), np.concatenate(reads),
                         np.concatenate(items))
+
+
+# ---- abea: Viterbi event alignment with traceback (benchmarks/abea, profile_hmm_align) ----
+
+
+class AbeaAlignItems(AbeaHmmItems):
+    """Items for abea.hmm_align: AbeaHmmItems over the nucleotide model, float32 [4096, 3] by k-mer rank over ACGT
+    (gen.abea_model); flags are 0 and every item has at least two rows (include/gb_bsw_abea_viterbi.h)."""
+
+    MODEL_SIZE = 4096
+
+
+def abea_align_kmer_ranks(strings, rc):
+    """Ranks [..., n_kmers] of the k-mers of ASCII strings [..., len] in the order profile_hmm_align visits them:
+    k-mer ki starts at ki for rc == 0 and at len - ki - 6 for rc == 1; two bits per base with A C G T = 0..3 and
+    any other byte 0 (eventalign.c:244-291, 434-446)."""
+    code = np.zeros(256, np.int64)
+    for i, ch in enumerate(b"ACGT"):
+        code[ch] = i
+    c = code[np.asarray(strings, np.uint8)]
+    n = c.shape[-1] - ABEA_K + 1
+    r = np.zeros(c.shape[:-1] + (n,), np.int64)
+    for i in range(ABEA_K):
+        r = r * 4 + c[..., i:i + n]
+    return np.where(np.asarray(rc)[..., None].astype(bool), r[..., ::-1], r)
+
+
+def abea_align_items(rng, shapes, model=None, rc=None, noise=0.7, non_acgt=0.0, outliers=0, outlier_every=0,
+                     homopolymer=0, quantum=None, scale=(0.95, 1.05), shift=(-4.0, 4.0), var=(0.9, 1.2), epb=(1.1, 3.0),
+                     lead=2):
+    """Synthetic windows for abea.hmm_align. `shapes` is a list of (count, n_kmers, n_rows): `count` reads, each
+    with one item, a random ACGT string of n_kmers + 5 bases (bytes turned into N with probability `non_acgt`, the
+    middle one always;
+    with `homopolymer` a run of that many equal bases in the middle) on the strand `rc` (0, 1, or None for a
+    random one per read), and n_rows >= 2 events drawn from the levels of the string's k-mers in the order the
+    strand visits them (row r from k-mer r * n_kmers // n_rows, `noise` stdv of Gaussian noise; `outliers` rows
+    per read, and every `outlier_every`-th row, lie 40 pA off), between `lead` other events on either side.
+    scale, shift, var and epb are a value or a (lo, hi) range per read; with `quantum` events are rounded to its
+    multiples."""
+    model = abea_model(rng) if model is None else model
+    N = ord("N")
+
+    def draw(v, n):
+        return rng.uniform(v[0], v[1], n) if isinstance(v, tuple) else np.full(n, float(v))
+
+    seqs, events, reads, items = [], [], [], []
+    seq_pos = ev_pos = n_reads = 0
+    for count, nk, rows in shapes:
+        L = nk + ABEA_K - 1
+        b = BASES[rng.integers(0, 4, (count, L))].copy()
+        if homopolymer:
+            h = min(int(homopolymer), L)
+            b[:, (L - h) // 2:(L - h) // 2 + h] = b[:, (L - h) // 2][:, None]
+        if non_acgt:
+            b[rng.random(b.shape) < non_acgt] = N
+            b[:, L // 2] = N
+        strand = rng.integers(0, 2, count) if rc is None else np.full(count, int(rc))
+        ranks = abea_align_kmer_ranks(b, strand)
+        lv = model[ranks[:, (np.arange(rows) * nk) // rows]]  # [count, rows, 3]
+        sc, sh, vr = (draw(v, count).astype(np.float32) for v in (scale, shift, var))
+        ev = (sc[:, None] * lv[..., 0] + sh[:, None]
+              + noise * lv[..., 1] * vr[:, None] * rng.standard_normal((count, rows)))
+        for _ in range(outliers):
+            at = rng.integers(0, rows, count)
+            ev[np.arange(count), at] += 40.0
+        if outlier_every:
+            ev[:, outlier_every - 1::outlier_every] += 40.0
+        n_ev = rows + 2 * lead
+        arr = rng.uniform(60, 120, (count, n_ev))
+        first = np.where(strand == 1, lead + rows - 1, lead)  # row 1's event
+        pos = first[:, None] + np.where(strand == 1, -1, 1)[:, None] * np.arange(rows)[None, :]
+        arr[np.arange(count)[:, None], pos] = ev
+        if quantum:
+            arr = np.round(arr / quantum) * quantum
+        rd = np.zeros(count, ABEA_HMM_READ_DTYPE)
+        rd["event_off"] = ev_pos + n_ev * np.arange(count, dtype=np.int64)
+        rd["n_events"] = n_ev
+        rd["scale"], rd["shift"], rd["var"] = sc, sh, vr
+        rd["log_var"] = np.log(vr.astype(np.float64)).astype(np.float32)
+        rd["events_per_base"] = draw(epb, count)
+        it = np.zeros(count, ABEA_HMM_ITEM_DTYPE)
+        it["seq_off"] = seq_pos + L * np.arange(count, dtype=np.int64)
+        it["seq_len"] = L
+        it["read"] = n_reads + np.arange(count)
+        it["event_start"] = first
+        it["event_stop"] = first + np.where(strand == 1, -1, 1) * (rows - 1)
+        it["rc"] = strand
+        seqs.append(b.reshape(-1))
+        events.append(arr.astype(np.float32).reshape(-1))
+        reads.append(rd)
+        items.append(it)
+        seq_pos += L * count
+        ev_pos += n_ev * count
+        n_reads += count
+    return AbeaAlignItems(model, np.concatenate(seqs), np.concatenate(events), np.concatenate(reads),
+                          np.concatenate(items))
