@@ -774,3 +774,125 @@ def abea_align_items(rng, shapes, model=None, rc=None, noise=0.7, non_acgt=0.0, 
         n_reads += count
     return AbeaAlignItems(model, np.concatenate(seqs), np.concatenate(events), np.concatenate(reads),
                           np.concatenate(items))
+
+
+# ---- chain: base-level alignment items (gb_chain_extd2, minimap2's ksw_extd2_sse) ----
+
+EXTD2_PARAMS_DTYPE = np.dtype([(f, "i1") for f in ("a", "b", "sc_ambi", "q", "e", "q2", "e2", "pad")])
+EXTD2_ITEM_DTYPE = np.dtype([("q_off", "<i8"), ("t_off", "<i8"), ("qlen", "<i4"), ("tlen", "<i4"), ("w", "<i4"),
+                             ("zdrop", "<i4"), ("end_bonus", "<i4"), ("flag", "<i4")])
+assert EXTD2_PARAMS_DTYPE.itemsize == 8 and EXTD2_ITEM_DTYPE.itemsize == 40
+# (a, b, sc_ambi, q, e, q2, e2) of minimap2's presets (options.c) that write CIGARs
+EXTD2_PRESETS = {"map-ont": (2, 4, 1, 4, 2, 24, 1), "asm5": (1, 19, 1, 39, 3, 81, 1), "asm20": (1, 4, 1, 6, 2, 26, 1),
+                 "sr": (2, 8, 1, 12, 2, 24, 1)}
+# mm_align1's four uses of ksw_extd2_sse: left extension, the two passes of a gap fill, right extension
+EXTD2_USES = (0x40 | 0x02 | 0x80, 0x08, 0, 0x40)
+
+
+class Extd2Items:
+    """Items for chain.extd2: `params` one EXTD2_PARAMS_DTYPE record, `seqs` the concatenated base codes (0..3,
+    4 for N) and `items` EXTD2_ITEM_DTYPE records (include/gb_chain_extd2.h)."""
+
+    def __init__(self, params, seqs, items):
+        self.params = np.ascontiguousarray(params, EXTD2_PARAMS_DTYPE).reshape(1)
+        self.seqs = np.ascontiguousarray(seqs, np.uint8)
+        self.items = np.ascontiguousarray(items, EXTD2_ITEM_DTYPE)
+
+    @property
+    def n(self):
+        return len(self.items)
+
+    def subset(self, idx):
+        """The same parameters and bases with items[idx]."""
+        return type(self)(self.params, self.seqs, self.items[np.asarray(idx, np.int64)])
+
+    @classmethod
+    def concat(cls, parts):
+        """The items of several sets over the first part's parameters, offsets shifted."""
+        items, pos = [], 0
+        for p in parts:
+            it = p.items.copy()
+            it["q_off"] += pos
+            it["t_off"] += pos
+            items.append(it)
+            pos += len(p.seqs)
+        return cls(parts[0].params, np.concatenate([p.seqs for p in parts]), np.concatenate(items))
+
+    def item(self, i):
+        """(query codes, target codes, item record) of item i."""
+        it = self.items[i]
+        return (self.seqs[it["q_off"]:it["q_off"] + it["qlen"]], self.seqs[it["t_off"]:it["t_off"] + it["tlen"]], it)
+
+
+def extd2_params(a, b, sc_ambi, q, e, q2, e2):
+    p = np.zeros(1, EXTD2_PARAMS_DTYPE)
+    for f, v in zip(("a", "b", "sc_ambi", "q", "e", "q2", "e2"), (a, b, sc_ambi, q, e, q2, e2)):
+        p[f] = np.array(v).astype(np.int8)
+    return p
+
+
+def extd2_query(rng, target, qlen, sub=0.06, indel=0.04, long_indel=0.0, repeat=0, n_rate=0.0, tail=0.0):
+    """A query of qlen codes derived from `target`: substitutions, indels of 1..3 bases, with rate `long_indel`
+    indels of 10..60 bases, the last `tail` part unrelated; `repeat` > 0 first turns the middle of the target (in
+    place) into a tandem repeat of that period, which is where left- and right-aligned gaps differ."""
+    tlen = len(target)
+    if repeat and tlen > 3 * repeat:
+        a = tlen // 4
+        unit = target[a:a + repeat].copy()
+        span = target[a:a + tlen // 2]
+        span[:] = np.resize(unit, len(span))
+    out, i = [], 0
+    while i < tlen and len(out) < qlen:
+        u = rng.random()
+        if u < long_indel:
+            L = int(rng.integers(10, 61))
+            if rng.random() < 0.5:
+                i += L
+            else:
+                out.extend(rng.integers(0, 4, L).tolist())
+        elif u < long_indel + indel:
+            L = int(rng.integers(1, 4))
+            if rng.random() < 0.5:
+                i += L
+            else:
+                out.extend(rng.integers(0, 4, L).tolist())
+        elif u < long_indel + indel + sub:
+            out.append(int((target[i] + rng.integers(1, 4)) % 4) if target[i] < 4 else int(rng.integers(0, 4)))
+            i += 1
+        else:
+            out.append(int(target[i]))
+            i += 1
+    out = np.array(out[:qlen], np.uint8)
+    if len(out) < qlen:
+        out = np.concatenate([out, rng.integers(0, 4, qlen - len(out)).astype(np.uint8)])
+    if tail > 0:
+        k = int(qlen * (1 - tail))
+        out[k:] = rng.integers(0, 4, qlen - k)
+    if n_rate > 0:
+        out[rng.random(qlen) < n_rate] = 4
+    return out
+
+
+def extd2_items(rng, shapes, params="map-ont", w=None, zdrop=None, end_bonus=None, flag=None, **mut):
+    """A seeded Extd2Items: `shapes` is a list of (qlen, tlen); per item a target is drawn (with N bases at
+    mut['n_rate']) and the query derived from it by extd2_query(**mut). `w`, `zdrop`, `end_bonus` and `flag` are
+    a value for every item, a sequence to draw from, or None: then w is drawn from (-1, 10, 50, 200, 751), zdrop
+    from (-1, 30, 400), end_bonus from (-1, 10) and flag from EXTD2_USES."""
+    if isinstance(params, str):
+        params = extd2_params(*EXTD2_PRESETS[params])
+
+    def draw(v, default):
+        v = default if v is None else v
+        return int(v) if np.isscalar(v) else int(v[rng.integers(0, len(v))])
+
+    seqs, items, pos = [], np.zeros(len(shapes), EXTD2_ITEM_DTYPE), 0
+    for k, (qlen, tlen) in enumerate(shapes):
+        target = rng.integers(0, 4, tlen).astype(np.uint8)
+        if mut.get("n_rate", 0.0) > 0:
+            target[rng.random(tlen) < mut["n_rate"]] = 4
+        query = extd2_query(rng, target, qlen, **mut) if tlen else rng.integers(0, 4, qlen).astype(np.uint8)
+        items[k] = (pos, pos + qlen, qlen, tlen, draw(w, (-1, 10, 50, 200, 751)), draw(zdrop, (-1, 30, 400)),
+                    draw(end_bonus, (-1, 10)), draw(flag, EXTD2_USES))
+        seqs += [query, target]
+        pos += qlen + tlen
+    return Extd2Items(params, np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), items)
