@@ -232,6 +232,39 @@ __device__ __forceinline__ double select_dist(uint32_t rmask, uint32_t h, double
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
+// The wave's sum in every lane by the butterfly acc += partner(lane ^ o), o = 32, 16 .. 1 (the early exit's
+// test: the order fixes the rounding). The exchanges below 32 go through ds_swizzle, whose lane pattern
+// is an immediate; as bpermutes each keeps an index register alive across the whole sweep.
+template <int O>
+__device__ __forceinline__ float swz_xor(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (O << 10) | 0x1F));
+}
+template <int O>
+__device__ __forceinline__ double swz_xor(double v) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_ds_swizzle((int)(b & 0xffffffffll), (O << 10) | 0x1F);
+  const int hi = __builtin_amdgcn_ds_swizzle((int)(b >> 32), (O << 10) | 0x1F);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum_xor(T acc) {
+  acc += __shfl_xor(acc, 32);
+  acc += swz_xor<16>(acc);
+  acc += swz_xor<8>(acc);
+  acc += swz_xor<4>(acc);
+  acc += swz_xor<2>(acc);
+  acc += swz_xor<1>(acc);
+  return acc;
+}
+
+// A value the optimiser takes as new where it stands. The exit kernel runs at the 64 registers of 8 waves
+// per SIMD: a per-lane address or offset that depends on the lane alone is otherwise computed once at
+// the kernel's top, kept for the whole stack, and spilled.
+__device__ __forceinline__ int fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // A lane's haplotype code of one column. The empty asm keeps the zero extension in the load's basic
 // block, where the byte load gives it for free; left to the optimiser it sinks to the step that uses
 // the code, behind lane 63's record write, and the code crosses the blocks as a byte that is masked
@@ -412,10 +445,19 @@ struct __attribute__((aligned(16))) StackEnt {
 // has passed column C + 1 when the group moves on, so the lane below it has consumed its column-C
 // outputs; between column C and its switch a lane computes garbage columns (code 0), as a lane of
 // phmm_stripe does beyond column C, and after the switch its negative columns give zeros through
-// the column codes 6 and 5. A switch replaces the lane's RowParams and state by the next turn's,
-// which are computed for all 64 lanes at once (the per-stripe set-up code) when the last group has
-// moved, into a second register set. Lane 0 passes through column 0 itself, so it needs no special
-// initial state and takes the record of column 0 like any other.
+// the column codes 6 and 5. A switch replaces the lane's RowParams and state by the next turn's.
+// When the last group has moved, every lane finds its row of the turn after (the binary search over
+// the entry table) and loads that row's quality bytes and those of the row below it: two registers
+// per lane (RowDesc: seven 7-bit qualities, with i and d of the row below already folded into their
+// m2m index, the match mask and the row's kind), held through the turn. The group's own switch
+// expands them straight into the live registers. It is a divergent branch taken by the group's 16
+// lanes (the other 48 are masked off by exec; no longer selects in a straight-line block): eight
+// independent table loads (the entries load_row reads; a va, v0 or dead lane loads entry 0 and drops
+// it) and a select per constant for the va / v0 / last / dead kinds, about 40 VALU instructions
+// for f32. No byte load -> table load chain is left at a switch, and no second set of constants for
+// 64 lanes lives through the turn (with one the f32 exit kernel spilled 40 registers and reloaded
+// them at every switch). Lane 0 passes through column 0 itself, so it needs no special initial state
+// and takes the record of column 0 like any other.
 // Records: lane 63 writes its row's z / w in place at its column, lane 0 reads the row above at its
 // own; lane 0 reads column c P - 63 steps after lane 63 wrote it (4 records are fetched a block
 // ahead: P >= 72, given by C >= 64) and lane 63 overwrites it 63 steps after that. Both go through
@@ -427,7 +469,8 @@ struct __attribute__((aligned(16))) StackEnt {
 // column C at step s*P + l + C), so the next one comes from the entry table; the summing block
 // variant runs from that row's switch to its column C.
 // Early exit: the test of phmm_stack, on the same rows with the same sum, at the first block
-// boundary after lane 63's row has written column C (44 or 48 steps into the next turn). No lane of
+// boundary after lane 63's row has written column C (44 or 48 steps into the next turn); lane 63's
+// row and testcase are read from the entry table as scalars when the last group switches. No lane of
 // the next turn has reached column C then (P > 63), so nothing of the dying testcase has been
 // stored: the rows in flight are abandoned and the sweep starts again at the next testcase's first
 // row, a va row, which ignores the records it is handed.
@@ -443,11 +486,6 @@ __host__ __device__ inline uint64_t stack_steps(int rows, int C, int sh, bool ro
   }
   return (uint64_t)turns * (uint64_t)(C + sh);
 }
-
-template <typename T>
-__device__ __forceinline__ void setup_row(int rho, bool dead, int r, int R, const uint8_t *__restrict__ rbase,
-                                          const DevTab<T> &tab, T init_Y, T z_top, RowParams<T> &P,
-                                          LaneState<T> &st);
 
 // The rolled sweep of a stack's rows from `base` (at least two turns, C >= 64). Returns the stacked
 // row the stack goes on from: T_rows, or the next testcase's first row after an early exit.
@@ -466,9 +504,16 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
   struct L63 {
     int r, R, start, out, may;
   };
-  // turn s's constants and initial state of every lane (phmm_stack's per-stripe set-up; no lane starts
-  // at column 1, so none takes lane 0's special cases), and lane 63's row for the early exit
-  auto setup = [&](int s, RowParams<T> &Q, LaneState<T> &q, L63 &L) {
+  // A lane's row of turn s, described in two registers (the binary search over the entry table and the
+  // row's quality bytes, once per turn for all 64 lanes); `expand` turns it into constants and state.
+  //   own: rmask | q << 8 | d << 16 | c << 24 of the lane's own row (rmask 0x3F for v0, all 0 for va / dead)
+  //   nxt: the row below in the same testcase: its m2m index (14 bits) | i << 14 | c << 21, and the row's
+  //        kind in the top four bits
+  constexpr uint32_t kReal = 1u << 28, kNext = 1u << 29, kVa = 1u << 30, kV0 = 1u << 31;
+  struct RowDesc {
+    uint32_t own, nxt;
+  };
+  auto describe = [&](int s) -> RowDesc {
     const int g = base + kWave * s + lane;
     int lo = 0, hi = na - 1;
     while (__builtin_amdgcn_ballot_w64(lo < hi)) {
@@ -479,30 +524,79 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
       }
     }
     const int start = __shfl(e_start, lo), R = __shfl(e_R, lo);
-    const uint32_t roff = (uint32_t)__shfl((int)e_read, lo);
-    const int r = g - start;
-    setup_row<T>(1, g >= T_rows, r, R, pool + roff, tab, init_Y, (T)0, Q, q);
-    if constexpr (kExit) {
-      L.r = __builtin_amdgcn_readlane(r, 63);
-      L.R = __builtin_amdgcn_readlane(R, 63);
-      L.start = __builtin_amdgcn_readlane(start, 63);
-      L.out = __builtin_amdgcn_readlane(__shfl((int)e_out, lo), 63);
-      L.may = __builtin_amdgcn_readlane((int)Q.rmask, 63) & kMayExit;
+    const uint8_t *rb = pool + (uint32_t)__shfl((int)e_read, lo);
+    const int r = g - start;  // 0: va, 1: v0, 2..R+1: read row r-2
+    const bool live = g < T_rows;
+    const bool real = live && r >= 2, below = live && r >= 1 && r <= R;  // a row of the read below it
+    RowDesc D;
+    D.own = (live && r == 1) ? 0x3Fu : 0u;
+    D.nxt = real ? kReal : (live ? (r == 0 ? kVa : kV0) : 0u);
+    if (real) {
+      const uint8_t *p = rb + (r - 2);
+      D.own = (uint32_t)p[0] | (uint32_t)(p[R] & 127) << 8 | (uint32_t)(p[3 * R] & 127) << 16 |
+              (uint32_t)(p[4 * R] & 127) << 24;
+    }
+    if (below) {
+      const uint8_t *p = rb + (r - 1);
+      const uint32_t qi = p[2 * R] & 127, qd = p[3 * R] & 127, qc = p[4 * R] & 127;
+      const uint32_t mn = qi <= qd ? qi : qd, mx = qi <= qd ? qd : qi;
+      D.nxt |= (((mx * (mx + 1)) >> 1) + mn) | qi << 14 | qc << 21 | (real ? kNext : 0u);
+    }
+    return D;
+  };
+  // The switch proper: the lanes in `mine` take their row's constants (the table entries load_row reads)
+  // and initial state (setup_row's, for a row that does not start at column 1), in place.
+  auto expand = [&](const RowDesc &D, bool mine, RowParams<T> &P, LaneState<T> &st) {
+    if (mine) {
+      const T zero = (T)0, one = (T)1;
+      const bool real = D.nxt & kReal, nextr = D.nxt & kNext, va = D.nxt & kVa, v0 = D.nxt & kV0;
+      const uint32_t q = (D.own >> 8) & 127, qd = (D.own >> 16) & 127, qc = D.own >> 24;
+      const uint32_t nqi = (D.nxt >> 14) & 127, nqc = (D.nxt >> 21) & 127;
+      const T tMY = tab.ph2pr[qd], tYY = tab.ph2pr[qc], tdm = tab.one_minus[q], tdx = tab.div3[q];
+      const T tMM = tab.m2m[D.nxt & 0x3FFF], tGAPM = tab.one_minus[nqc], tMX = tab.ph2pr[nqi], tXX = tab.ph2pr[nqc];
+      P.rmask = D.own & 0xFF;
+      P.pMY = real ? tMY : zero;
+      P.pYY = real ? tYY : (va ? one : zero);
+      P.dmatch = real ? tdm : (v0 ? one : zero);
+      P.dmis = real ? tdx : zero;
+      P.nMM = nextr ? tMM : (v0 ? tGAPM : zero);
+      P.nGAPMx = nextr ? tGAPM : zero;
+      P.nGAPM = nextr ? tGAPM : (va ? one : zero);
+      P.nMX = nextr ? tMX : zero;
+      P.nXX = nextr ? tXX : zero;
+      st.Mp = st.wo = zero;
+      st.Yp = st.zo = va ? init_Y : zero;  // va hands init_Y down from its first step: (0*0 + 0*0) + init_Y*1
+      st.zd = v0 ? init_Y : zero;          // va's output at the column before
     }
   };
+  // lane 63's row of turn s for the early exit, as scalars: its entry is the last one starting at or
+  // before it (the entries are in stacked-row order)
+  auto row63 = [&](int s, const RowParams<T> &P) -> L63 {
+    const int g = base + kWave * s + kWave - 1;
+    const int e = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < na && e_start <= g)) - 1;
+    L63 L;
+    L.start = __builtin_amdgcn_readlane(e_start, e);
+    L.R = __builtin_amdgcn_readlane(e_R, e);
+    L.out = __builtin_amdgcn_readlane((int)e_out, e);
+    L.r = g - L.start;
+    L.may = __builtin_amdgcn_readlane((int)P.rmask, 63) & kMayExit;
+    return L;
+  };
   auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };  // wave-uniform, for the compiler
-  RowParams<T> P, Pn;
-  LaneState<T> st, sn;
-  L63 c63 = {0, 0, 0, 0, 0}, n63 = {0, 0, 0, 0, 0};
-  setup(0, P, st, c63);
-  setup(1, Pn, sn, n63);
+  RowParams<T> P;
+  LaneState<T> st;
+  expand(describe(0), true, P, st);
+  L63 c63 = {0, 0, 0, 0, 0};
+  if constexpr (kExit) c63 = row63(0, P);
+  RowDesc nd = describe(1);  // the next turn's rows
   T sumM = (T)0, sumX = (T)0;
-  const uint8_t *hl = hcol - lane;  // hl[t]: the code of the lane's column at step t
+  const int ln = fresh(lane);
+  const uint8_t *hl = hcol - ln;  // hl[t]: the code of the lane's column at step t
   // pp[t]: lane 0's record in every lane but 63, which holds its own. Lane 63's first columns of the
   // sweep, -63 .. -16, have no record: until step kFirst they go to the last records of the pad
   // beyond column C, which are read as garbage columns only
   constexpr int kFirst = kWave - kRecPad;
-  Brec<T> *pp = last_lane ? bnd + (C + kBndPad - kFirst) : bnd;
+  Brec<T> *pp = ln == kWave - 1 ? bnd + (C + kBndPad - kFirst) : bnd;
   int first_t = kFirst;
   int s3 = 0;         // the turn lane 63 is in
   int sw = 0;         // next switch: group `sw` moves to turn s3 + 1 at step sw_t
@@ -535,8 +629,8 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
           __syncthreads();
           T acc = (T)0;
 #pragma unroll 1
-          for (int c = 1 + lane; c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
-          for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+          for (int c = 1 + fresh(lane); c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
+          acc = wave_sum_xor(acc);
           if (__builtin_amdgcn_readfirstlane(acc < (T)0.25e-28f ? 1 : 0)) {
             const int next = c63.start + c63.R + 2;
             if (lane == 0) {
@@ -557,35 +651,21 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
       first_t = INT_MAX;
     }
     if (t == sw_t) {
-      // group `sw` takes the next turn's constants and state (selects, so the block is straight-line)
+      // group `sw` takes the next turn's constants and state
       const bool mine = lane / G == sw;
-      auto take = [mine](T &cur, T nxt) { cur = mine ? nxt : cur; };
-      take(P.pMY, Pn.pMY);
-      take(P.pYY, Pn.pYY);
-      take(P.dmatch, Pn.dmatch);
-      take(P.dmis, Pn.dmis);
-      take(P.nMM, Pn.nMM);
-      take(P.nGAPM, Pn.nGAPM);
-      take(P.nGAPMx, Pn.nGAPMx);
-      take(P.nMX, Pn.nMX);
-      take(P.nXX, Pn.nXX);
-      P.rmask = mine ? Pn.rmask : P.rmask;
-      take(st.Mp, (T)0);
-      take(st.wo, (T)0);
-      take(st.Yp, sn.Yp);
-      take(st.zo, sn.zo);
-      take(st.zd, sn.zd);
-      take(sumM, (T)0);
-      take(sumX, (T)0);
-      hl -= mine ? Pd : 0;
-      if (sw == 0) pp -= last_lane ? 0 : Pd;
+      expand(nd, mine, P, st);
+      if (mine) {
+        sumM = sumX = (T)0;
+        hl -= Pd;
+      }
+      if (sw == 0) pp -= last_lane ? 0 : fresh(Pd);
       if (sw == NG - 1) {
         // lane 63 is at column -(G - 1) >= -kRecPad and goes on writing. The turn after this one is
         // set up now (beyond the last turn: dead rows, never switched to)
         s3 = uni(s3 + 1);
         if (last_lane) pp = bnd - (kWave - 1) - s3 * Pd;
-        c63 = n63;
-        setup(s3 + 1, Pn, sn, n63);
+        if constexpr (kExit) c63 = row63(s3, P);
+        nd = describe(s3 + 1);
         sw = 0;
         sw_t = uni(s3 + 1 < nturn ? (s3 + 1) * Pd : INT_MAX);
       } else {
@@ -821,8 +901,8 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
       if (r63 >= 2 && r63 <= R63 && (__builtin_amdgcn_readlane((int)P.rmask, 63) & kMayExit)) {
         T acc = (T)0;
 #pragma unroll 1
-        for (int c = 1 + lane; c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
-        for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+        for (int c = 1 + fresh(lane); c <= C; c += kWave) acc += bnd[c].z + bnd[c].w;
+        acc = wave_sum_xor(acc);
         // the sum is the same in every lane; readfirstlane tells the compiler so (a divergent loop
         // bound would turn the whole stripe loop into per-lane control flow)
         if (__builtin_amdgcn_readfirstlane(acc < (T)0.25e-28f ? 1 : 0)) {
@@ -1094,9 +1174,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8
 // `scratch` (scratch_stride bytes per workgroup, global memory: lane 63's record stores and lane 0's
 // loads of the next stripe are ordered by the stripe's __syncthreads), and both passes take the
 // stacks through a persistent grid (counter[2] f32, counter[3] f64).
-// The LDS kernels' registers are held to the waves per SIMD their LDS allows (f32 8, f64 4): with
-// phmm_rolled's second register set the compiler's own choice is 85-106 VGPRs for f32; held to 64, what
-// it spills is touched at the switches only, not in the 4-step blocks.
+// The LDS kernels' registers are held to the waves per SIMD their LDS allows (f32 8, f64 4). As built
+// by the Makefile (-O3 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp)
+// the f32 kernels take 59 and, with the exit, 64 registers without a spill (phmm_rolled's RowDesc,
+// fresh(), wave_sum_xor) and the f64 kernel 107 of 128; without the max-ilp scheduler 58 / 64 / 94.
 template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : (sizeof(T) == 4 ? 8 : 4), 8))) void phmm_forward(
     const Stack *__restrict__ stacks, int nstacks,
