@@ -50,6 +50,10 @@ def _declare(L):
     L.gb_phmm_batch_timing.argtypes = [vp, fp, fp, fp]
     L.gb_phmm_batch_stats.argtypes = [vp, i64p, i64p, i64p]
     L.gb_phmm_batch_exit_stats.argtypes = [vp, i64p, i64p]
+    L.gb_phmm_batch_predict_stats.argtypes = [vp, i64p, i64p, i64p, i64p]
+    L.gb_phmm_batch_predicted.argtypes = [vp, vp]
+    L.gb_phmm_batch_stacks.argtypes = [vp, i64p]
+    L.gb_phmm_certificate.argtypes = [vp, ci, vp, vp]
     L.gb_phmm_batch_destroy.argtypes = [vp]
 
 

@@ -61,6 +61,12 @@ constexpr int kStackRows = 2048;  // rows per stack (a testcase taller than this
 constexpr int kPlanBuckets = 128;
 constexpr int kPlanCount = 8, kPlanCursor = kPlanCount + kPlanBuckets, kPlanTotal = kPlanCursor + kPlanBuckets;
 constexpr int kCountWords = kPlanTotal + 8;
+// behind the plan's total, the predictor's words: the gate's sample (testcases, predicted), testcases
+// predicted, confirmed and redone, and the redo launch's unit count and cursor
+constexpr int kPredSampled = kPlanTotal + 1, kPredSamplePred = kPlanTotal + 2, kPredPredicted = kPlanTotal + 3;
+constexpr int kPredConfirmed = kPlanTotal + 4, kPredRedone = kPlanTotal + 5, kRedoUnits = kPlanTotal + 6;
+constexpr int kRedoNext = kPlanTotal + 7;
+static_assert(kRedoNext < kCountWords, "counter words");
 constexpr int kMaxF64Parts = 8;
 constexpr int kM2M = ((127 * 128) >> 1) + 128;  // set_mm_prob indices for quals < 128
 
@@ -168,6 +174,64 @@ static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R)
     if (G > 1e30) return inf;
   }
   return G;
+}
+
+// The predictor's certificate (phmm_predict, phmm_verify). A predicted testcase skips the f32 pass and is
+// taken by the f64 pass; phmm_verify then needs the f64 result to prove that the f32 result, which nobody
+// computed, is below MIN_ACCEPTED. Both results are sums over the same alignment paths of products of
+// table entries, times INITIAL_CONSTANT / haplen: f32 of the f32 tables' entries with f32 roundings, f64
+// of the f64 tables'. A path visits at most R + C cells and takes at most two entries per cell (a
+// transition and, in M, the emission), so with rho >= 1 the largest ratio of an f32 entry to its f64 entry
+// among the entries the read's rows use, the exact f32-table sum is at most rho^(2 (R + C) + 2) times the
+// exact f64-table sum. Every f32 operation on these non-negative terms gives at most its exact value
+// times 1 + 2^-24 (plus 2^-150 where it rounds into the denormals: below 4e-35 over a whole matrix, see
+// the early exit), every f64 operation at least its exact value times 1 - 2^-53 (f64 results of interest
+// are ~2^800: its underflow is nowhere near), and a result depends on at most D = 4 (R + C) + C + 4
+// operations in a chain: 4 a cell (the emission product, a transition product, the bracket's two sums),
+// the last row's C + 1 additions, the division of the initial constant. Hence
+//   f32_result <= K * f64_result * 2^-900 + 4e-35,  K = rho^(2 (R + C) + 2) * ((1 + 2^-24) / (1 - 2^-53))^D.
+// cert_log_rho: log(rho) of a read, or +inf for a read that is never certified: an entry that is 0 in
+// f64 and positive in f32, an insertion or deletion quality of 0..3 (where GKL clamps pMM at 0 and a
+// state's outflow exceeds 1), a base or continuation quality of 0 (ph2pr = 1). cert_K: the bound for a
+// haplotype of C columns. The pack certifies a read (kMayPredict in its first quality byte, whose bit 7
+// no kernel reads) when cert_K(R, kMaxHaplen) <= kCertMax: K grows with C, so the flag holds for every
+// haplotype the read meets. log(rho), rounded up to f32, follows the read's five byte rows in the pool, and
+// phmm_verify computes the testcase's own K from it.
+constexpr double kCertMax = 2.0;
+constexpr uint8_t kMayPredict = 0x80;
+// CertTab: per quality value the largest f32 / f64 ratio of the entries a row takes with it (+inf for an
+// entry that is 0 in f64 and positive in f32), so that a row costs five lookups at pack time.
+struct CertTab {
+  double q[kQualTab];  // one_minus[q], div3[q]
+  double p[kQualTab];  // ph2pr[i], ph2pr[d]
+  double c[kQualTab];  // ph2pr[c], one_minus[c]
+  double m[kM2M];      // m2m
+};
+static void build_cert_tab(const HostTables<float> &tf, const HostTables<double> &td, CertTab &T) {
+  auto ratio = [](float f, double d) {
+    return d > 0 ? std::max(1.0, (double)f / d) : (f > 0 ? std::numeric_limits<double>::infinity() : 1.0);
+  };
+  for (int x = 0; x < kQualTab; x++) {
+    T.q[x] = std::max(ratio(tf.one_minus[x], td.one_minus[x]), ratio(tf.div3[x], td.div3[x]));
+    T.p[x] = ratio(tf.ph2pr[x], td.ph2pr[x]);
+    T.c[x] = std::max(T.p[x], ratio(tf.one_minus[x], td.one_minus[x]));
+  }
+  for (int k = 0; k < kM2M; k++) T.m[k] = ratio(tf.m2m[k], td.m2m[k]);
+}
+static double cert_log_rho(const CertTab &T, const uint8_t *q, const uint8_t *qi, const uint8_t *qd,
+                           const uint8_t *qc, int R) {
+  double rho = 1.0;
+  for (int r = 0; r < R; r++) {
+    const int a = q[r] & 127, i = qi[r] & 127, d = qd[r] & 127, c = qc[r] & 127;
+    if (i <= 3 || d <= 3 || a == 0 || c == 0) return std::numeric_limits<double>::infinity();
+    const int mn = std::min(i, d), mx = std::max(i, d), m = ((mx * (mx + 1)) >> 1) + mn;
+    rho = std::max(rho, std::max(std::max(T.q[a], T.p[i]), std::max(std::max(T.p[d], T.c[c]), T.m[m])));
+  }
+  return std::log(rho);
+}
+__host__ __device__ inline double cert_K(double log_rho, int R, int C) {
+  const double steps = (double)R + (double)C, D = 4.0 * steps + (double)C + 4.0;
+  return exp((2.0 * steps + 2.0) * log_rho + D * 5.9604644e-8);  // >= log1p(2^-24) - log1p(-2^-53)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -717,14 +781,15 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
   return T_rows;
 }
 
-// One stack. f32 pass: every testcase (kExit: with the early exit below); f64 pass: those whose f32
-// result is below MIN_ACCEPTED (all of them when `force`). Returns the number of testcases computed.
+// One stack. f32 pass: every testcase `sel` selects (kExit: with the early exit below); f64 pass: those
+// whose f32 result is below MIN_ACCEPTED (all of them when `force`). Returns the number of testcases computed.
 // kRoll && roll: the stack's runs of at least two turns over C >= 64 columns take phmm_rolled.
 template <typename T, bool kF64Pass, bool kExit = false, bool kRoll = false>
 __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__restrict__ stk_tc, const TcDesc *__restrict__ descs,
                           const uint8_t *__restrict__ pool, const DevTab<T> &tab, T *__restrict__ raw_out,
                           const float *__restrict__ raw_f, bool force, uint8_t *smem_raw, int part = 0,
-                          int parts = 1, unsigned long long *exit_stats = nullptr, bool roll = false) {
+                          int parts = 1, unsigned long long *exit_stats = nullptr, bool roll = false,
+                          const uint8_t *__restrict__ sel = nullptr, int sel_want = 0) {
   const int lane = threadIdx.x;
   const int C = (int)S.C;
   // LDS: boundary records for columns [-kRecPad, C+kBndPad) and the haplotype codes for columns
@@ -742,6 +807,9 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
   if (act) {
     d = descs[stk_tc[S.first + lane]];
     if constexpr (kF64Pass) act = force || raw_f[d.out_idx] < 1e-28f;  // MIN_ACCEPTED, pairhmm_common.h:16
+    // f32 pass: without the testcases phmm_predict took (sel = pred, 0); the redo launch: only those
+    // phmm_verify sent back (sel = redo, 1)
+    else if (sel) act = sel[d.out_idx] == (uint8_t)sel_want;
   }
   const uint64_t am = __builtin_amdgcn_ballot_w64(act);
   if (!am) return 0;
@@ -1178,7 +1246,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8
 // by the Makefile (-O3 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp)
 // the f32 kernels take 59 and, with the exit, 64 registers without a spill (phmm_rolled's RowDesc,
 // fresh(), wave_sum_xor) and the f64 kernel 107 of 128; without the max-ilp scheduler 58 / 64 / 94.
-template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false>
+// kRedo: the f32 pass again over the stacks phmm_redo_plan listed (a persistent grid through
+// counter[kRedoNext]; no work, no stack), for the testcases marked in `sel`, without the early exit.
+template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false, bool kRedo = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : (sizeof(T) == 4 ? 8 : 4), 8))) void phmm_forward(
     const Stack *__restrict__ stacks, int nstacks,
                                                     const uint32_t *__restrict__ stk_tc,
@@ -1186,11 +1256,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : 
                                                     const uint8_t *__restrict__ pool, DevTab<T> tab,
                                                     T *__restrict__ raw_out, const float *__restrict__ raw_f,
                                                     int *__restrict__ counter, int force, uint8_t *scratch,
-                                                    size_t scratch_stride, const uint32_t *__restrict__ units) {
+                                                    size_t scratch_stride, const uint32_t *__restrict__ units,
+                                                    const uint8_t *__restrict__ sel, int sel_want) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   uint8_t *rec = kLong ? scratch + (size_t)blockIdx.x * scratch_stride : smem_raw;
   const bool roll = (force >> 16) & 1;  // the LDS stacks' rolled sweep (phmm_rolled; GB_PHMM_ROLL)
-  if constexpr (kF64Pass || kLong) {
+  if constexpr (kRedo) {
+    const int nwork = __builtin_amdgcn_readfirstlane(counter[kRedoUnits]);
+    while (true) {
+      int k = 0;
+      if (threadIdx.x == 0) k = atomicAdd(counter + kRedoNext, 1);
+      k = __builtin_amdgcn_readfirstlane(__shfl(k, 0));
+      if (k >= nwork) break;
+      k = __builtin_amdgcn_readfirstlane((int)units[k]);
+      phmm_stack<T, false, false, true>(stacks[k], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1, nullptr,
+                                        roll, sel, sel_want);
+      __syncthreads();
+    }
+  } else if constexpr (kF64Pass || kLong) {
     int done = 0;
     int *next = counter + (kLong ? (kF64Pass ? 3 : 2) : 1);
     // f64 pass over the LDS stacks: `parts` work units per stack (the top byte of `force`), so a job
@@ -1211,7 +1294,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : 
     if (kF64Pass && threadIdx.x == 0 && done) atomicAdd(counter, done);
   } else {
     phmm_stack<T, false, kExit, true>(stacks[blockIdx.x], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1,
-                                      reinterpret_cast<unsigned long long *>(counter + 4), roll);
+                                      reinterpret_cast<unsigned long long *>(counter + 4), roll, sel, sel_want);
   }
 }
 
@@ -1278,17 +1361,250 @@ __global__ __launch_bounds__(256) void f64_plan_order(int nunits, const uint8_t 
   if (key) units[off[key] + base[key] + rank] = (uint32_t)u;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fallback predictor. A testcase whose f32 result is below MIN_ACCEPTED is computed twice: by the f32
+// pass, which throws the result away, and by the f64 pass. phmm_predict picks such testcases before the
+// f32 pass from an integer estimate of the likelihood (tests/phmm_predict_ref.py restates it in numpy,
+// decision for decision): the cheapest ungapped diagonal among -63 .. C - R + 63, a mismatch costing
+// 1.4 / 2.5 / 3.9 (base quality below 14 / below 28 / from 28) and an overhang of n rows 4.5 + (n - 1), in
+// units of 0.01 log10; predicted when the cost exceeds -log10(MIN_ACCEPTED * 2^-120 * C) + kPredMargin.
+// A predicted testcase gets pred = 1 and raw f32 = 0: the f32 pass compacts it out of its stack and the
+// f64 pass takes it. The estimate is not a bound. phmm_verify confirms a prediction from the f64 result
+// and the read's certificate (cert_K: f32 <= K * f64 * 2^-900 + 4e-35, so f32 < MIN_ACCEPTED is
+// proved); what it cannot confirm is marked `redo`, and a second launch of the f32 kernel computes those
+// testcases' f32 results after all (phmm_redo_plan lists their stacks), as if they had never been
+// predicted. Only certified reads are predicted.
+// The kernel: a wave per stack. The haplotype's columns become four bit planes in LDS (base A / C / T /
+// G, each also set for N and outside the haplotype, whose rows cost their overhang), column c at bit c + 64. Per testcase, 64 rows at a time, the
+// read's rows become seven wave-uniform bit planes by ballot (the row's match-mask bits 0..3, three
+// quality classes). A lane owns one diagonal of a 64-diagonal chunk: for 32 rows the haplotype planes'
+// bits of its diagonal are a funnel shift of two LDS words (three words serve 64 rows), mismatch =
+// ~OR(read_b & hap_b), three popcounts: about 18 VALU instructions per 32 rows x 64 diagonals.
+// Gate: whether a batch falls back at all is a property of its packed testcases, so it is decided where
+// they are packed. batch_fill launches the kernel in kPredSample mode behind its uploads: kGateTake
+// testcases of one stack in 16 (of every stack up to kGateAll stacks; chosen by the stack's place in the
+// testcase list, so both sweeps' launch orders sample alike; positions that move through the stack with
+// that place, since a stack's first testcases are the first of its haplotype in input order; a
+// wave's time is the latency of its testcases one after the other, so it takes few), counted with their
+// predictions and nothing else written, read back at the synchronisation the fill ends with. With fewer
+// than 1 in kGateDen predicted the gate is closed and gb_phmm_batch_run launches exactly what it launched
+// without the predictor: a batch that does not fall back pays nothing per step. A one-shot call
+// (gb_phmm_compute) pays the sample at every fill and the redo launch's latency at every step, about
+// 0.5 ms, so there the predictor is used from kPredMinCells cells a call only; a batch made by
+// gb_phmm_batch_create is sampled once and run many times, and is predicted at any size.
+// kPredOpen: everything with no gate (GB_PHMM_PREDICT=open), kPredAll: every certified testcase.
+constexpr int kPredMargin = -100, kPredThresh = 6412, kPredPad = 63;
+constexpr int kPredMaxRows = 2046;
+constexpr int kPlaneWords = 320;  // >= (kLdsHaplen + 64 + 256) / 32 + 3, even
+constexpr int kPredChunks = 4;    // 64-diagonal chunks sharing one pass over the read's rows
+constexpr int kGateDen = 8, kGateTake = 2, kGateAll = 1024;  // (one stack in 16: the top 4 bits of a hash)
+constexpr int64_t kPredMinCells = 5000000000ll;  // one-shot calls: 0.5 ms fixed against 12 % of a 4 ms step
+static_assert(kPlaneWords % 2 == 0 && kPlaneWords >= (kLdsHaplen + 64 + 256) / 32 + 3, "plane words");
+enum PredictMode { kPredSample = 0, kPredAll = 2, kPredOpen = 3 };
+
+__device__ __forceinline__ int pred_overhang(int n) { return n > 0 ? 350 + 100 * n : 0; }
+
+__global__ __launch_bounds__(64) void phmm_predict(const Stack *__restrict__ stacks, int nstacks,
+                                                   const uint32_t *__restrict__ stk_tc,
+                                                   const TcDesc *__restrict__ descs, const uint8_t *__restrict__ pool,
+                                                   float *__restrict__ raw_f, uint8_t *__restrict__ pred,
+                                                   int *__restrict__ counter, int mode) {
+  __shared__ uint32_t plane[4][kPlaneWords];
+  const int lane = threadIdx.x;
+  const int first = (int)blockIdx.x, stride = (int)gridDim.x;
+  int seen = 0, npred = 0;
+  for (int k = first; k < nstacks; k += stride) {
+    const Stack S = stacks[k];
+    const int C = (int)S.C;
+    // the sample takes kGateTake of the stack's testcases, half a stack apart, from a position that moves
+    // with the stack's index
+    const int cnt = (int)S.count;
+    // which stacks and testcases the sample takes depends on the stack's place in the testcase list, not
+    // on the launch order (which differs between the two sweeps): the same batch, the same gate
+    if (mode == kPredSample && nstacks > kGateAll && ((S.first * 2654435761u) >> 28) != 0) continue;
+    const int n_take = mode == kPredSample ? min(kGateTake, cnt) : cnt;
+    const int a_first = mode == kPredSample ? (int)((S.first >> 4) % (uint32_t)cnt) : 0;
+    const int a_step = mode == kPredSample ? (cnt + 1) / 2 : 1;
+    seen += n_take;
+    if (C > kLdsHaplen) continue;
+    const uint8_t *hcode = pool + S.hap_off;
+    const int nw = (C + 64 + 256) / 32 + 2;
+    __syncthreads();
+    for (int j = 0; 2 * j < nw; j++) {
+      const int c = 64 * j + lane - 64;
+      const uint32_t code = (c >= 0 && c < C) ? hcode[c] : 255u;
+      // outside the haplotype every base "matches": those rows cost their overhang, added per diagonal
+      uint64_t m[4];
+      for (int b = 0; b < 4; b++) m[b] = __builtin_amdgcn_ballot_w64(code == (uint32_t)b || code >= 4u);
+      if (lane < 8) {
+        const uint64_t v = lane < 2 ? m[0] : lane < 4 ? m[1] : lane < 6 ? m[2] : m[3];
+        plane[lane >> 1][2 * j + (lane & 1)] = (uint32_t)(v >> (32 * (lane & 1)));
+      }
+    }
+    __syncthreads();
+    const int lcC = [&]() {
+      const int msb = 31 - __builtin_clz((uint32_t)C);
+      const uint32_t l2 = ((uint32_t)msb << 8) | ((((uint32_t)C << (31 - msb)) >> 23) & 0xFFu);
+      return (int)((l2 * 7706u) >> 16);
+    }();
+    const int thr = kPredThresh - lcC + kPredMargin;
+    for (int j = 0; j < n_take; j++) {
+      const int a = (a_first + j * a_step) % cnt;
+      const TcDesc d = descs[stk_tc[S.first + a]];
+      const int R = (int)(d.dims & 0xffff);
+      const uint8_t *rb = pool + d.read_off;
+      if (!(rb[R] & kMayPredict) || R > kPredMaxRows) continue;
+      int best = 1 << 30;
+      if (mode != kPredAll) {
+        const int dhi = C - R + kPredPad;
+        for (int g0 = 0; g0 - kPredPad <= dhi; g0 += 64 * kPredChunks) {
+          const int nch = min(kPredChunks, (dhi + kPredPad - g0) / 64 + 1);
+          const int e0 = 1 + g0 + lane;  // the lane's diagonal of chunk 0, + 64: its bit at row 0
+          const uint32_t sh = (uint32_t)e0 & 31u;
+          const uint32_t *w0 = &plane[0][e0 >> 5];
+          uint32_t n0[kPredChunks], n1[kPredChunks], n2[kPredChunks];
+          for (int c = 0; c < kPredChunks; c++) n0[c] = n1[c] = n2[c] = 0;
+          for (int r64 = 0; r64 < R; r64 += 64) {
+            const int row = r64 + lane;
+            const bool in = row < R;
+            const uint32_t rm = in ? rb[row] : 0u, qv = in ? (uint32_t)(rb[R + row] & 127) : 0u;
+            uint64_t rp[4], qp[3];
+            for (int b = 0; b < 4; b++) rp[b] = __builtin_amdgcn_ballot_w64((rm >> b) & 1u);
+            qp[0] = __builtin_amdgcn_ballot_w64(in && qv < 14u);
+            qp[1] = __builtin_amdgcn_ballot_w64(in && qv >= 14u && qv < 28u);
+            qp[2] = __builtin_amdgcn_ballot_w64(in && qv >= 28u);
+            // rows r64 .. r64 + 31 take the planes' words j, j + 1 of the lane's diagonal, rows r64 + 32 ..
+            // words j + 1, j + 2; rows from R on are in no quality class
+            const uint32_t *w = w0 + (r64 >> 5);
+            const bool two = r64 + 32 < R;
+#pragma unroll
+            for (int c = 0; c < kPredChunks; c++) {
+              if (c < nch) {
+                uint32_t ha[4], hb[4];
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                  const uint32_t x0 = w[p * kPlaneWords + 2 * c], x1 = w[p * kPlaneWords + 2 * c + 1];
+                  const uint32_t x2 = w[p * kPlaneWords + 2 * c + 2];
+                  ha[p] = __builtin_amdgcn_alignbit(x1, x0, sh);
+                  hb[p] = __builtin_amdgcn_alignbit(x2, x1, sh);
+                }
+                const uint32_t ma = ~(((uint32_t)rp[0] & ha[0]) | ((uint32_t)rp[1] & ha[1]) | ((uint32_t)rp[2] & ha[2]) |
+                                      ((uint32_t)rp[3] & ha[3]));
+                n0[c] += __builtin_popcount(ma & (uint32_t)qp[0]);
+                n1[c] += __builtin_popcount(ma & (uint32_t)qp[1]);
+                n2[c] += __builtin_popcount(ma & (uint32_t)qp[2]);
+                if (two) {
+                  const uint32_t mb = ~(((uint32_t)(rp[0] >> 32) & hb[0]) | ((uint32_t)(rp[1] >> 32) & hb[1]) |
+                                        ((uint32_t)(rp[2] >> 32) & hb[2]) | ((uint32_t)(rp[3] >> 32) & hb[3]));
+                  n0[c] += __builtin_popcount(mb & (uint32_t)(qp[0] >> 32));
+                  n1[c] += __builtin_popcount(mb & (uint32_t)(qp[1] >> 32));
+                  n2[c] += __builtin_popcount(mb & (uint32_t)(qp[2] >> 32));
+                }
+              }
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < kPredChunks; c++) {
+            const int dg = g0 + 64 * c + lane - kPredPad;
+            if (c < nch && dg <= dhi) {
+              const int n_lo = min(R, max(0, -dg)), n_hi = min(R - n_lo, max(0, R + dg - C));
+              const int cost = 140 * (int)n0[c] + 250 * (int)n1[c] + 390 * (int)n2[c] + pred_overhang(n_lo) +
+                               pred_overhang(n_hi);
+              best = min(best, cost);
+            }
+          }
+        }
+        best = __builtin_amdgcn_readlane(gb::scan_min<(1 << 30)>(best), 63);
+      }
+      if (best > thr) {
+        npred++;
+        if (lane == 0 && mode != kPredSample) {
+          pred[d.out_idx] = 1;
+          raw_f[d.out_idx] = 0.f;
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    if (mode == kPredSample && seen) atomicAdd(counter + kPredSampled, seen);
+    if (mode == kPredSample && npred) atomicAdd(counter + kPredSamplePred, npred);
+    if (mode != kPredSample && npred) atomicAdd(counter + kPredPredicted, npred);
+  }
+}
+
+// After the f64 pass, a thread per testcase: a predicted testcase whose f64 result proves the f32 result
+// below MIN_ACCEPTED (cert_K) is confirmed and counts, with all its cells, in the early exit's statistics;
+// every other predicted testcase is marked for the redo launch.
+__global__ __launch_bounds__(256) void phmm_verify(const TcDesc *__restrict__ descs, int n,
+                                                   const uint8_t *__restrict__ pool,
+                                                   const uint8_t *__restrict__ pred, const double *__restrict__ rd,
+                                                   uint8_t *__restrict__ redo, int *__restrict__ counter) {
+  if (__builtin_amdgcn_readfirstlane(counter[kPredPredicted]) == 0) return;
+  int nok = 0, nre = 0;
+  unsigned long long cells = 0;
+  // a small grid strides over the testcases: the counters take one set of atomics per wave
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
+    if (!pred[k]) continue;
+    const TcDesc d = descs[k];
+    const int R = (int)(d.dims & 0xffff), C = (int)(d.dims >> 16);
+    const uint8_t *lp = pool + d.read_off + 5 * (size_t)R;  // the read's log(rho), unaligned
+    const uint32_t lb = (uint32_t)lp[0] | (uint32_t)lp[1] << 8 | (uint32_t)lp[2] << 16 | (uint32_t)lp[3] << 24;
+    const double K = cert_K((double)__builtin_bit_cast(float, lb), R, C);
+    if (rd[k] * 0x1p-900 * K + 4e-35 < (double)1e-28f) {
+      cells += (unsigned long long)R * (unsigned long long)C;
+      nok++;
+    } else {
+      redo[k] = 1;
+      nre++;
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    cells += __shfl_xor(cells, o);
+    nok += __shfl_xor(nok, o);
+    nre += __shfl_xor(nre, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (nok) {
+      atomicAdd(counter + kPredConfirmed, nok);
+      atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4), (unsigned long long)nok);
+      atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4) + 1, cells);
+    }
+    if (nre) atomicAdd(counter + kPredRedone, nre);
+  }
+}
+
+// The stacks with a testcase to redo, in any order (a testcase's result does not depend on its stack).
+__global__ __launch_bounds__(256) void phmm_redo_plan(const Stack *__restrict__ stacks, int nstacks,
+                                                      const uint32_t *__restrict__ stk_tc,
+                                                      const uint8_t *__restrict__ redo, int *__restrict__ counter,
+                                                      uint32_t *__restrict__ units) {
+  if (__builtin_amdgcn_readfirstlane(counter[kPredRedone]) == 0) return;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nstacks) return;
+  const Stack S = stacks[k];
+  bool any = false;
+  for (uint32_t a = 0; a < S.count && !any; a++) any = redo[stk_tc[S.first + a]] != 0;  // out_idx = testcase index
+  if (any) units[atomicAdd(counter + kRedoUnits, 1)] = (uint32_t)k;
+}
+
 // gb_phmm_init's warm-up launch (no work)
 __global__ void phmm_warm(int *count) {
   if (threadIdx.x == 0 && blockIdx.x == 0) count[3] = 0;
 }
 
 // Device log10 epilogue (IntelPairHmmCSource.cpp:73-79); the host path recomputes it bit-exactly.
-__global__ void phmm_finalize(const float *__restrict__ rf, const double *__restrict__ rd,
-                              const uint8_t *__restrict__ used, double *__restrict__ out, int n,
-                              float log10_init_f, double log10_init_d) {
+// After a redo launch (`redo` set): a redone testcase whose f32 result passes MIN_ACCEPTED is answered from
+// f32, as in the reference: its f64 result reads 0 like that of any testcase that never fell back, and it
+// leaves the count of fallbacks (counter[0], gb_phmm_batch_stats).
+__global__ void phmm_finalize(const float *__restrict__ rf, double *__restrict__ rd,
+                              const uint8_t *__restrict__ redo, double *__restrict__ out, int n,
+                              float log10_init_f, double log10_init_d, int *__restrict__ counter) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (redo && redo[i] && rf[i] >= 1e-28f) {
+    rd[i] = 0.0;
+    atomicSub(counter, 1);
+  }
   out[i] = (rf[i] < 1e-28f) ? (log10(rd[i]) - log10_init_d) : (double)(log10f(rf[i]) - log10_init_f);
 }
 
@@ -1306,6 +1622,7 @@ struct DeviceTables {
 std::mutex g_mu;
 HostTables<float> *g_hf = nullptr;
 HostTables<double> *g_hd = nullptr;
+CertTab *g_cert = nullptr;
 std::unordered_map<int, DeviceTables *> g_dev;
 
 int ensure_host_tables() {
@@ -1314,6 +1631,9 @@ int ensure_host_tables() {
     auto *d = new HostTables<double>();
     build_tables(*f);
     build_tables(*d);
+    auto *c = new CertTab();
+    build_cert_tab(*f, *d, *c);
+    g_cert = c;
     g_hf = f;
     g_hd = d;
   }
@@ -1355,7 +1675,8 @@ int get_device_tables(DeviceTables **out) {
   st = upload_tables(*g_hd, &t->d);
   if (st) return st;
   for (auto fn : {(const void *)phmm_forward<float, false>, (const void *)phmm_forward<float, false, false, true>,
-                  (const void *)phmm_forward<double, true>, (const void *)phmm_forward2<0>, (const void *)phmm_forward2<6>, (const void *)phmm_forward2<8>})
+                  (const void *)phmm_forward<double, true>,
+                  (const void *)phmm_forward<float, false, false, false, true>, (const void *)phmm_forward2<0>, (const void *)phmm_forward2<6>, (const void *)phmm_forward2<8>})
     GB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   g_dev[dev] = t;
   *out = t;
@@ -1437,6 +1758,13 @@ struct gb_phmm_batch {
   bool f64_plan = true;  // the f64 pass's units by cost (f64_plan; GB_PHMM_F64_PLAN=0: stack order)
   bool f32_exit = true;  // the f32 pass's early exit (phmm_stack kExit; GB_PHMM_EXIT=0 turns it off)
   bool roll = true;      // both passes' rolled sweep of the LDS stacks (phmm_rolled; GB_PHMM_ROLL=0: a fill per stripe)
+  int predict = 1;       // the fallback predictor (phmm_predict; GB_PHMM_PREDICT=0: off, all: every certified testcase, open: no gate)
+  bool resident = false;  // made by gb_phmm_batch_create (packed once, run many times), not a one-shot workspace
+  bool gate_open = false; // batch_fill's sample: enough of the batch is predicted for the predictor to run
+  int gate_n = 0, gate_pred = 0;  // the sample's testcases and predictions
+  uint8_t *d_pred = nullptr;  // per testcase: predicted (skips the f32 pass), and behind it d_redo
+  uint8_t *d_redo = nullptr;  // per testcase: prediction not confirmed, f32 result computed by the redo launch
+  size_t pred_bytes = 0;      // of d_rd, d_pred and d_redo together (adjacent in the arena)
   // host scratch of the fills (grow-only, host_reserve)
   std::vector<uint32_t> hid;
   std::vector<Stack> stacks;
@@ -1480,11 +1808,11 @@ struct HostClock {
 int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
   const size_t nn = std::max(n, 1);
   auto up = [](size_t x) { return gb::round_up<size_t>(x, 256); };
-  const size_t sz[8] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
-                        up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
-                        up(sizeof(Stack) * nn),  // at most one stack per testcase
-                        up(sizeof(uint32_t) * nn * kMaxF64Parts), up(nn * kMaxF64Parts)};
-  const size_t arena = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6] + sz[7];
+  const size_t sz[10] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
+                         up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
+                         up(sizeof(Stack) * nn),  // at most one stack per testcase
+                         up(sizeof(uint32_t) * nn * kMaxF64Parts), up(nn * kMaxF64Parts), up(nn), up(nn)};
+  const size_t arena = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6] + sz[7] + sz[8] + sz[9];
   // every sz[] grows with nn, so an arena that holds this sum was carved for at least these sizes
   if (arena > b->d_arena.capacity()) {
     // the per-testcase arrays carved from one allocation (a cold process pays per hipMalloc)
@@ -1495,6 +1823,7 @@ int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
     b->d_stacks = nullptr;
     b->d_units = nullptr;
     b->d_ukey = nullptr;
+    b->d_pred = b->d_redo = nullptr;
     if (int st = b->d_arena.reserve(arena)) return st;
     uint8_t *a = b->d_arena;
     b->d_desc = (TcDesc *)a;
@@ -1503,6 +1832,11 @@ int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
     a += sz[1];
     b->d_rd = (double *)a;
     a += sz[2];
+    b->d_pred = a;  // d_rd, d_pred and d_redo are zeroed by one fill
+    a += sz[8];
+    b->d_redo = a;
+    a += sz[9];
+    b->pred_bytes = sz[2] + sz[8] + sz[9];
     b->d_out = (double *)a;
     a += sz[3];
     b->d_stk_tc = (uint32_t *)a;
@@ -1611,6 +1945,10 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     int64_t cells = 0;
   };
   std::vector<Chunk> ch(nth);
+  // one-shot calls below kPredMinCells do without the predictor (phmm_predict, "Gate")
+  int64_t pre_cells = 0;
+  for (int k = 0; k < n; k++) pre_cells += (int64_t)tcs[k].rslen * tcs[k].haplen;
+  const bool cert_wanted = b->resident || pre_cells >= kPredMinCells;
   auto pack_chunk = [&](Chunk &C) {
     std::unordered_map<ReadKey, uint32_t, KeyHash> read_at;
     std::unordered_map<HapKey, uint32_t, KeyHash> hap_at;
@@ -1637,7 +1975,7 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
           roff = ri->second;
         } else {
           roff = (uint32_t)pool.size();
-          pool.resize(pool.size() + 5 * (size_t)t.rslen);
+          pool.resize(pool.size() + 5 * (size_t)t.rslen + sizeof(float));  // and the certificate's log(rho)
           uint8_t *rec = pool.data() + roff;
           for (int r = 0; r < t.rslen; r++) {
             rec[r] = read_match_mask(base_code(t.rs[r]));
@@ -1649,6 +1987,19 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
           // the early exit's gate: bit 7 of every row's match mask (select_dist reads bits 0..6)
           if (exit_growth(b->tabs->hf, rec, t.rslen) <= kExitGrowthMax)
             for (int r = 0; r < t.rslen; r++) rec[r] |= kMayExit;
+          // the predictor's certificate: bit 7 of the first quality byte (the kernels read bits 0..6)
+          if (t.rslen > 0) rec[t.rslen] &= 127;
+          // (a call that will not be predicted, see may_predict below, certifies nothing)
+          const double lr = cert_wanted ? cert_log_rho(*g_cert, rec + t.rslen, rec + 2 * t.rslen, rec + 3 * t.rslen,
+                                                       rec + 4 * t.rslen, t.rslen)
+                                        : std::numeric_limits<double>::infinity();
+          float lrf = 0.f;
+          if (t.rslen > 0 && cert_K(lr, t.rslen, kMaxHaplen) <= kCertMax) {
+            rec[t.rslen] |= kMayPredict;
+            lrf = (float)lr;
+            if ((double)lrf < lr) lrf = std::nextafterf(lrf, 1.f);
+          }
+          std::memcpy(rec + 5 * (size_t)t.rslen, &lrf, sizeof(float));
           read_at.emplace(rk, roff);
         }
       }
@@ -1772,6 +2123,12 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   // rolled stripes (phmm_rolled) in both passes
   b->roll = true;
   if (const char *e = getenv("GB_PHMM_ROLL")) b->roll = atoi(e) != 0;
+  // the fallback predictor (phmm_predict): on; GB_PHMM_PREDICT=0 off, =all every certified testcase with
+  // the gate off (tests: every passing testcase then takes the verify -> redo path), =open the estimate
+  // with the gate off (tests of jobs too small for the gate's sample)
+  b->predict = 1;
+  if (const char *e = getenv("GB_PHMM_PREDICT"))
+    b->predict = strcmp(e, "all") == 0 ? 2 : strcmp(e, "open") == 0 ? 3 : (atoi(e) != 0 ? 1 : 0);
   const bool roll = b->roll && b->rpl == 1;
   int stack_rows = kStackRows;
   if (total_rows / stack_rows < 4ll * 32 * b->cus) stack_rows = 1024;
@@ -1912,7 +2269,26 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     GB_HIP(hipMemcpyAsync(b->d_stacks, h_stacks, sizeof(Stack) * ns_all, hipMemcpyHostToDevice, b->stream));
   }
   GB_HIP(hipMemcpyAsync(b->d_pool, h_pool, pool_bytes, hipMemcpyHostToDevice, b->stream));
+  // the predictor's gate (phmm_predict): sampled here, behind the uploads, and read at the fill's own
+  // synchronisation; one-shot calls below kPredMinCells do without the predictor
+  const int ns_short = ns_all - n_long;
+  const bool may_predict = b->predict && b->f32_exit && b->rpl == 1 && ns_short > 0 &&
+                           cert_wanted;
+  int gate[2] = {0, 0};
+  b->gate_open = may_predict && b->predict >= 2;
+  if (may_predict && b->predict == 1) {
+    GB_HIP(hipMemsetAsync(b->d_count, 0, kCountWords * sizeof(int), b->stream));
+    const int sg = std::min(ns_short, b->cus * 16);
+    hipLaunchKernelGGL(phmm_predict, dim3(sg), dim3(kWave), 0, b->stream, (const Stack *)b->d_stacks, ns_short,
+                       (const uint32_t *)b->d_stk_tc, (const TcDesc *)b->d_desc, (const uint8_t *)b->d_pool.get(),
+                       b->d_rf, b->d_pred, b->d_count.get(), (int)kPredSample);
+    GB_HIP(hipGetLastError());
+    GB_HIP(hipMemcpyAsync(gate, b->d_count + kPredSampled, sizeof(gate), hipMemcpyDeviceToHost, b->stream));
+  }
   GB_HIP(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next fill
+  b->gate_n = gate[0];
+  b->gate_pred = gate[1];
+  if (may_predict && b->predict == 1) b->gate_open = (int64_t)gate[1] * kGateDen >= (int64_t)gate[0] && gate[1] > 0;
   clk.mark("upload");
   b->n = n;
   b->nstacks = ns_all - n_long;
@@ -2093,6 +2469,7 @@ int gb_phmm_batch_create(const gb_testcase *tcs, int n, gb_phmm_batch **out) {
   if (st) return st;
   gb_phmm_batch *b = nullptr;
   if ((st = batch_new(tabs, &b))) return st;
+  b->resident = true;
   if ((st = batch_fill(b, tcs, n))) {
     gb_phmm_batch_destroy(b);
     return st;
@@ -2109,7 +2486,9 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
   const int n = b->n;
   GB_HIP(hipEventRecord(b->ev[0], b->stream));
   GB_HIP(hipMemsetAsync(b->d_count, 0, kCountWords * sizeof(int), b->stream));
-  GB_HIP(hipMemsetAsync(b->d_rd, 0, sizeof(double) * std::max(n, 1), b->stream));
+  // (a run with the predictor zeroes d_rd together with d_pred and d_redo behind it)
+  const bool predict = n > 0 && b->gate_open && b->f32_exit && !b->force_f64 && b->rpl == 1 && b->nstacks > 0;
+  GB_HIP(hipMemsetAsync(b->d_rd, 0, predict ? b->pred_bytes : sizeof(double) * std::max(n, 1), b->stream));
   if (n > 0) {
     const size_t rec = (size_t)(b->max_haplen + kBndPad + kRecPad), codes = (size_t)(b->max_haplen + kBndPad + kWave);
     const size_t lds_f = sizeof(Brec<float>) * rec + codes + 16;
@@ -2119,6 +2498,15 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
     const int ns = b->nstacks, nl = b->n_long;
     const Stack *d_long = b->d_stacks + ns;
     if (b->f32_exit) f32k = phmm_forward<float, false, false, true>;
+    // the fallback predictor, on the exit's switch too (GB_PHMM_EXIT=0 keeps every raw f32), when the
+    // fill's sample opened the gate; the f32 pass then leaves the predicted testcases out
+    const uint8_t *skip = predict ? b->d_pred : nullptr;
+    if (predict) {
+      const int pg = std::min(ns, b->cus * 16);
+      hipLaunchKernelGGL(phmm_predict, dim3(pg), dim3(kWave), 0, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
+                         b->d_pool, b->d_rf, b->d_pred, b->d_count, b->predict == 2 ? (int)kPredAll : (int)kPredOpen);
+      GB_HIP(hipGetLastError());
+    }
     if (!b->force_f64) {
       if (ns > 0 && b->rpl == 2) {
         const size_t lds_f2 = sizeof(Brec<float>) * (size_t)(b->max_haplen + kBndPad2 + kRecPad) +
@@ -2129,13 +2517,14 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
       } else if (ns > 0) {
         hipLaunchKernelGGL(f32k, dim3(ns), dim3(kWave), lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                            b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr,
-                           b->d_count, b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr);
+                           b->d_count, b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr,
+                           skip, 0);
       }
       if (nl > 0)
         hipLaunchKernelGGL((phmm_forward<float, false, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
                            nl, b->d_stk_tc, b->d_desc, b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf,
                            (const float *)nullptr, b->d_count, 0, b->d_scratch, b->scratch_stride,
-                           (const uint32_t *)nullptr);
+                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0);
       GB_HIP(hipGetLastError());
     }
     GB_HIP(hipEventRecord(b->ev[1], b->stream));
@@ -2154,18 +2543,34 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
                          b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd, (const float *)b->d_rf,
                          b->d_count, (b->force_f64 ? 1 : 0) | (b->f64_parts << 8) | (b->roll ? 1 << 16 : 0),
                          (uint8_t *)nullptr, (size_t)0,
-                         b->f64_plan ? (const uint32_t *)b->d_units : nullptr);
+                         b->f64_plan ? (const uint32_t *)b->d_units : nullptr, (const uint8_t *)nullptr, 0);
     }
     if (nl > 0)
       hipLaunchKernelGGL((phmm_forward<double, true, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
                          nl, b->d_stk_tc, b->d_desc, b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd,
                          (const float *)b->d_rf, b->d_count, b->force_f64 ? 1 : 0, b->d_scratch, b->scratch_stride,
-                         (const uint32_t *)nullptr);
+                         (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0);
+    if (predict) {
+      // confirm the predictions from the f64 results; the f32 pass again for those not confirmed (its
+      // grid finds no work when there are none), over d_units, which the f64 pass is done with
+      const dim3 sg((unsigned)((ns + 255) / 256)), tb(256);
+      const dim3 vg((unsigned)std::min((n + 255) / 256, b->cus));
+      hipLaunchKernelGGL(phmm_verify, vg, tb, 0, b->stream, (const TcDesc *)b->d_desc, n,
+                         (const uint8_t *)b->d_pool.get(), (const uint8_t *)b->d_pred,
+                         (const double *)b->d_rd, b->d_redo, b->d_count);
+      hipLaunchKernelGGL(phmm_redo_plan, sg, tb, 0, b->stream, (const Stack *)b->d_stacks, ns,
+                         (const uint32_t *)b->d_stk_tc, (const uint8_t *)b->d_redo, b->d_count, b->d_units);
+      hipLaunchKernelGGL((phmm_forward<float, false, false, false, true>), dim3(std::min(ns, b->cus * 8)), dim3(kWave),
+                         lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc, b->d_pool,
+                         dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr, b->d_count,
+                         b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)b->d_units,
+                         (const uint8_t *)b->d_redo, 1);
+    }
     GB_HIP(hipGetLastError());
     GB_HIP(hipEventRecord(b->ev[2], b->stream));
-    hipLaunchKernelGGL(phmm_finalize, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->d_rf,
-                       b->d_rd, (const uint8_t *)nullptr, b->d_out, n, t->hf.log10_init,
-                       t->hd.log10_init);
+    hipLaunchKernelGGL(phmm_finalize, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->d_rf, b->d_rd,
+                       predict ? (const uint8_t *)b->d_redo : nullptr, b->d_out, n, t->hf.log10_init,
+                       t->hd.log10_init, b->d_count);
     GB_HIP(hipGetLastError());
   } else {
     GB_HIP(hipEventRecord(b->ev[1], b->stream));
@@ -2269,6 +2674,62 @@ int gb_phmm_batch_exit_stats(gb_phmm_batch *b, int64_t *dropped, int64_t *cells_
   }
   if (dropped) *dropped = (int64_t)c[0];
   if (cells_skipped) *cells_skipped = (int64_t)c[1];
+  return GB_OK;
+}
+
+int gb_phmm_batch_predict_stats(gb_phmm_batch *b, int64_t *sampled, int64_t *predicted, int64_t *confirmed,
+                                int64_t *redone) {
+  GB_ARG(b, "gb_phmm_batch_predict_stats: null batch");
+  int c[kCountWords] = {0};
+  if (b->ran) {
+    GB_HIP(hipStreamSynchronize(b->stream));
+    GB_HIP(hipMemcpy(c, b->d_count, sizeof(c), hipMemcpyDeviceToHost));
+  }
+  if (sampled) *sampled = b->gate_n;
+  if (predicted) *predicted = c[kPredPredicted];
+  if (confirmed) *confirmed = c[kPredConfirmed];
+  if (redone) *redone = c[kPredRedone];
+  return GB_OK;
+}
+
+int gb_phmm_batch_stacks(gb_phmm_batch *b, int64_t *stacks) {
+  GB_ARG(b && stacks, "gb_phmm_batch_stacks: null argument");
+  *stacks = (int64_t)b->nstacks + b->n_long;
+  return GB_OK;
+}
+
+int gb_phmm_batch_predicted(gb_phmm_batch *b, uint8_t *pred) {
+  GB_ARG(b && pred, "gb_phmm_batch_predicted: null argument");
+  if (!b->ran) {
+    gb::set_error("gb_phmm_batch_predicted: batch has not been run");
+    return GB_ERR_STATE;
+  }
+  if (b->n == 0) return GB_OK;
+  GB_HIP(hipStreamSynchronize(b->stream));
+  int c[kCountWords] = {0};
+  GB_HIP(hipMemcpy(c, b->d_count, sizeof(c), hipMemcpyDeviceToHost));
+  // a run without the predictor leaves d_pred as it was: nothing predicted
+  if (c[kPredPredicted] == 0)
+    std::memset(pred, 0, (size_t)b->n);
+  else
+    GB_HIP(hipMemcpy(pred, b->d_pred, (size_t)b->n, hipMemcpyDeviceToHost));
+  return GB_OK;
+}
+
+int gb_phmm_certificate(const gb_testcase *tcs, int n, double *K, uint8_t *certified) {
+  GB_ARG(n >= 0 && (n == 0 || tcs), "gb_phmm_certificate: bad testcase array (n=%d)", n);
+  if (int st = validate_testcases(tcs, n)) return st;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    ensure_host_tables();
+  }
+  for (int k = 0; k < n; k++) {
+    const gb_testcase &t = tcs[k];
+    const double lr = cert_log_rho(*g_cert, (const uint8_t *)t.q, (const uint8_t *)t.i, (const uint8_t *)t.d,
+                                   (const uint8_t *)t.c, t.rslen);
+    if (K) K[k] = cert_K(lr, t.rslen, t.haplen);
+    if (certified) certified[k] = cert_K(lr, t.rslen, kMaxHaplen) <= kCertMax ? 1 : 0;
+  }
   return GB_OK;
 }
 

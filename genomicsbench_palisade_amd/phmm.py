@@ -3,6 +3,7 @@ IntelPairHmmCSource.cpp:29-115): init_pairhmm() ~ initPairHMM(), compute_likelih
 computelikelihoodsboth(), all executed by the HIP kernels in libgb.so (csrc/phmm.hip)."""
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -66,6 +67,20 @@ def compute_f64(tcs: TestcaseArray):
     return rd
 
 
+PredictStats = collections.namedtuple("PredictStats", "sampled predicted confirmed redone")
+
+
+def certificate(tcs: TestcaseArray):
+    """The predictor's certificate per testcase (host only): (K, certified) with
+    f32_result <= K * f64_result * 2^-900 + 4e-35; K is inf for a read that is never certified."""
+    K = np.full(max(tcs.n, 1), np.inf)
+    cert = np.zeros(max(tcs.n, 1), np.uint8)
+    if tcs.n:
+        check(lib().gb_phmm_certificate(ctypes.addressof(tcs.arr), tcs.n, K.ctypes.data, cert.ctypes.data),
+              "gb_phmm_certificate")
+    return K[:tcs.n], cert[:tcs.n].astype(bool)
+
+
 class DeviceBatch:
     """A packed, HBM-resident testcase batch (gb_phmm_batch_*): create once, run many times."""
 
@@ -110,6 +125,26 @@ class DeviceBatch:
         check(lib().gb_phmm_batch_exit_stats(self.h, ctypes.byref(d), ctypes.byref(c)),
               "gb_phmm_batch_exit_stats")
         return d.value, c.value
+
+    def predict_stats(self):
+        """The fallback predictor in the last run, as a PredictStats: testcases of the gate's sample,
+        predicted (they skipped the f32 pass), confirmed by their f64 result, redone in f32."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        check(lib().gb_phmm_batch_predict_stats(self.h, *[ctypes.byref(x) for x in v]),
+              "gb_phmm_batch_predict_stats")
+        return PredictStats(*[x.value for x in v])
+
+    def stacks(self):
+        """Stacks the batch was packed into."""
+        v = ctypes.c_int64()
+        check(lib().gb_phmm_batch_stacks(self.h, ctypes.byref(v)), "gb_phmm_batch_stacks")
+        return v.value
+
+    def predicted(self):
+        """Per testcase: 1 where the last run predicted the fallback."""
+        p = np.zeros(max(self._tcs.n, 1), np.uint8)
+        check(lib().gb_phmm_batch_predicted(self.h, p.ctypes.data), "gb_phmm_batch_predicted")
+        return p[:self._tcs.n]
 
     def close(self):
         if self.h:

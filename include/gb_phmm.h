@@ -84,7 +84,23 @@ int gb_phmm_batch_stats(gb_phmm_batch *b, int64_t *testcases, int64_t *cells, in
  * raw f32 reads 0; they fall back to f64 as they would have) and the read-row x haplotype cells it
  * did not compute for them. */
 int gb_phmm_batch_exit_stats(gb_phmm_batch *b, int64_t *dropped, int64_t *cells_skipped);
+/* The fallback predictor (csrc/phmm.hip phmm_predict; GB_PHMM_PREDICT=0 off, =all every certified testcase
+ * with no gate, =open the estimate with no gate): testcases of the gate's sample (taken when the batch is packed),
+ * testcases predicted to fall back (they skipped the f32 pass), those the f64 result confirmed, and those
+ * it did not, whose f32 result was computed afterwards. `confirmed` also counts in
+ * gb_phmm_batch_exit_stats's dropped testcases, with all their cells. */
+int gb_phmm_batch_predict_stats(gb_phmm_batch *b, int64_t *sampled, int64_t *predicted, int64_t *confirmed,
+                                int64_t *redone);
+/* Stacks the batch was packed into (testcases sharing a haplotype, swept by one wave). */
+int gb_phmm_batch_stacks(gb_phmm_batch *b, int64_t *stacks);
+/* The testcases a run predicted (1) or not (0), one byte per testcase. */
+int gb_phmm_batch_predicted(gb_phmm_batch *b, uint8_t *pred);
 int gb_phmm_batch_destroy(gb_phmm_batch *b);
+
+/* The predictor's certificate, host only: per testcase the bound K with
+ * f32_result <= K * f64_result * 2^-900 + 4e-35 (+inf for a read that is never certified), and whether
+ * the pack certifies the read (K <= 2 for every haplotype length). */
+int gb_phmm_certificate(const gb_testcase *tcs, int n, double *K, uint8_t *certified);
 
 #ifdef __cplusplus
 }
