@@ -690,9 +690,10 @@ int gb_fmi_smem_onepos(gb_fmi_index *idx, const uint8_t *enc_qdb, const int32_t 
   int64_t tot = 0;
   for (auto &v : recs) tot += (int64_t)v.size();
   *nout = tot;
+  // a refused call writes nothing but *nout (the need)
+  GB_ARG(!out || tot <= out_cap, "gb_fmi_smem_onepos: %lld SMEMs exceed out_cap %lld", (long long)tot, (long long)out_cap);
   if (next_pos) std::copy(np.begin(), np.end(), next_pos);
   if (!out) return GB_OK;
-  GB_ARG(tot <= out_cap, "gb_fmi_smem_onepos: %lld SMEMs exceed out_cap %lld", (long long)tot, (long long)out_cap);
   int64_t o = 0;
   for (auto &v : recs)
     for (auto &r : v) put(out + o++, r);
@@ -719,9 +720,9 @@ int gb_fmi_smem_allpos(gb_fmi_index *idx, const uint8_t *enc_qdb, const int32_t 
     max_round = std::max(max_round, rn[t]);
   }
   *nout = tot;
+  GB_ARG(!out || tot <= out_cap, "gb_fmi_smem_allpos: %lld SMEMs exceed out_cap %lld", (long long)tot, (long long)out_cap);
   if (rounds) std::copy(rn.begin(), rn.end(), rounds);
   if (!out) return GB_OK;
-  GB_ARG(tot <= out_cap, "gb_fmi_smem_allpos: %lld SMEMs exceed out_cap %lld", (long long)tot, (long long)out_cap);
   // round-major, tasks in order within a round: a merge of the per-task lists (rounds ascending)
   std::vector<size_t> cur(ntasks, 0);
   std::vector<int32_t> live;

@@ -33,6 +33,9 @@ def _decl():
     L.gb_fmi_search.argtypes = [vp, i32]
     L.gb_fmi_debug_ctl.argtypes = [vp, vp]
     L.gb_fmi_get_smems.argtypes = [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp]
+    L.gb_fmi_smem_onepos.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp]
+    L.gb_fmi_smem_allpos.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
+    L.gb_fmi_last_seeds.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, vp, vp]
     L.gb_fmi_sync.argtypes = [vp]
     L.gb_fmi_results.argtypes = [vp, i32, vp, i64, vp, vp, vp]
     L.gb_fmi_timing.argtypes = [vp, vp, vp, vp]
@@ -121,6 +124,94 @@ class Index:
         check(L.gb_fmi_get_smems(self.h, codes.ctypes.data, num_reads, rl, min_seed_len, nthreads, out.ctypes.data,
                                  len(out), ctypes.byref(n), ctypes.byref(calls)), "gb_fmi_get_smems")
         return out[:n.value], calls.value
+
+    # The per-call phases of the FMI_search class (csrc/fmi_tasks.hip). Reads: flat codes with
+    # lens[r] / offs[r] per read. The *_raw forms pass every argument through as given (None = a null
+    # pointer; out, next_pos and rounds are the caller's arrays, written in place) and return
+    # (status, *nout, backwardExt calls); *nout starts at -1.
+    @staticmethod
+    def _in(a, dtype):
+        return None if a is None else np.ascontiguousarray(a, dtype)
+
+    @staticmethod
+    def _p(a):
+        return None if a is None else a.ctypes.data
+
+    @staticmethod
+    def _outp(a, dtype):
+        assert a is None or (a.dtype == dtype and a.flags.c_contiguous), "output arrays are written in place"
+        return None if a is None else a.ctypes.data
+
+    def smem_onepos_raw(self, codes, lens, offs, nrid, query_pos, min_intv, rid, ntasks, min_seed_len, out, out_cap,
+                        next_pos):
+        codes, lens, offs = self._in(codes, np.uint8), self._in(lens, np.int32), self._in(offs, np.int32)
+        query_pos, min_intv, rid = self._in(query_pos, np.int16), self._in(min_intv, np.int32), self._in(rid, np.int32)
+        n, calls = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        st = _decl().gb_fmi_smem_onepos(self.h, self._p(codes), self._p(lens), self._p(offs), nrid, self._p(query_pos),
+                                        self._p(min_intv), self._p(rid), ntasks, min_seed_len,
+                                        self._outp(out, SMEM_DTYPE), out_cap, ctypes.byref(n),
+                                        self._outp(next_pos, np.int16), ctypes.byref(calls))
+        return st, n.value, calls.value
+
+    def smem_allpos_raw(self, codes, lens, offs, nrid, min_intv, rid, ntasks, min_seed_len, out, out_cap, rounds):
+        codes, lens, offs = self._in(codes, np.uint8), self._in(lens, np.int32), self._in(offs, np.int32)
+        min_intv, rid = self._in(min_intv, np.int32), self._in(rid, np.int32)
+        n, calls = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        st = _decl().gb_fmi_smem_allpos(self.h, self._p(codes), self._p(lens), self._p(offs), nrid, self._p(min_intv),
+                                        self._p(rid), ntasks, min_seed_len, self._outp(out, SMEM_DTYPE), out_cap,
+                                        ctypes.byref(n), self._outp(rounds, np.int32), ctypes.byref(calls))
+        return st, n.value, calls.value
+
+    def last_seeds_raw(self, codes, lens, offs, nreads, max_intv, min_seed_len, out, out_cap):
+        codes, lens, offs = self._in(codes, np.uint8), self._in(lens, np.int32), self._in(offs, np.int32)
+        max_intv = self._in(max_intv, np.int32)
+        n, calls = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        st = _decl().gb_fmi_last_seeds(self.h, self._p(codes), self._p(lens), self._p(offs), nreads, self._p(max_intv),
+                                       min_seed_len, self._outp(out, SMEM_DTYPE), out_cap, ctypes.byref(n),
+                                       ctypes.byref(calls))
+        return st, n.value, calls.value
+
+    def get_smems_raw(self, codes, num_reads, readlength, min_seed_len, nthreads, out, out_cap):
+        codes = self._in(codes, np.uint8)
+        n, calls = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        st = _decl().gb_fmi_get_smems(self.h, self._p(codes), num_reads, readlength, min_seed_len, nthreads,
+                                      self._outp(out, SMEM_DTYPE), out_cap, ctypes.byref(n), ctypes.byref(calls))
+        return st, n.value, calls.value
+
+    def smem_onepos(self, codes, lens, offs, query_pos, min_intv, rid, min_seed_len: int = 19):
+        """FMI_search::getSMEMsOnePosOneThread: task t = (rid[t], query_pos[t], min_intv[t]) -> (SMEMs in
+        task order, next_pos per task, backwardExt calls)."""
+        nt = len(rid)
+        a = (codes, lens, offs, len(lens), query_pos, min_intv, rid, nt, min_seed_len)
+        st, n, _ = self.smem_onepos_raw(*a, None, 0, None)
+        check(st, "gb_fmi_smem_onepos")
+        out, nxt = np.zeros(max(n, 1), SMEM_DTYPE), np.zeros(max(nt, 1), np.int16)
+        st, n, calls = self.smem_onepos_raw(*a, out, len(out), nxt)
+        check(st, "gb_fmi_smem_onepos")
+        return out[:n], nxt[:nt], calls
+
+    def smem_allpos(self, codes, lens, offs, min_intv, rid, min_seed_len: int = 19):
+        """FMI_search::getSMEMsAllPosOneThread: task t = (rid[t], min_intv[t]), every x start -> (SMEMs
+        round-major in the reference's order, rounds per task, backwardExt calls)."""
+        nt = len(rid)
+        a = (codes, lens, offs, len(lens), min_intv, rid, nt, min_seed_len)
+        st, n, _ = self.smem_allpos_raw(*a, None, 0, None)
+        check(st, "gb_fmi_smem_allpos")
+        out, rounds = np.zeros(max(n, 1), SMEM_DTYPE), np.zeros(max(nt, 1), np.int32)
+        st, n, calls = self.smem_allpos_raw(*a, out, len(out), rounds)
+        check(st, "gb_fmi_smem_allpos")
+        return out[:n], rounds[:nt], calls
+
+    def last_seeds(self, codes, lens, offs, max_intv, min_seed_len: int = 20):
+        """FMI_search::bwtSeedStrategyAllPosOneThread over every read (max_intv[i] per read) -> (SMEMs in
+        read order, backwardExt calls)."""
+        a = (codes, lens, offs, len(lens), max_intv, min_seed_len)
+        st, n, _ = self.last_seeds_raw(*a, None, 0)
+        check(st, "gb_fmi_last_seeds")
+        out = np.zeros(max(n, 1), SMEM_DTYPE)
+        st, n, calls = self.last_seeds_raw(*a, out, len(out))
+        check(st, "gb_fmi_last_seeds")
+        return out[:n], calls
 
     def close(self):
         if self.h:

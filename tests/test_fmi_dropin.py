@@ -127,7 +127,8 @@ def _oracle_phases(oi, codes, lens, bc, maxlen, min_seed_len):
                           (300_000, 1500, 151, 512, 3, 3, False, "", "0"), (150_000, 600, 300, 128, 2, 6, False, "", "")])
 def test_class_driver_matches_oracle(tmp_path, size, nreads, L, batch, threads, seed, build, tile, wave):
     """tile: GB_FMI_TASK_TILE, tasks per launch of the per-call kernels (the scratch bound; 100 forces
-    several tiles per call, with the overflow pass inside each). wave: GB_FMI_TASK_WAVE -- reads up to
+    several tiles per call -- no task overflows its slot at min_seed_len 19, the re-run of overflowing
+    tasks is test_fmi_tasks.py's). wave: GB_FMI_TASK_WAVE -- reads up to
     256 bases run a wave per task (fmi_wave.h), "0" forces a lane per task; 300-base reads always take
     the lane kernel."""
     ref = gen.fmi_reference(size, seed=seed, repeat_frac=0.15)

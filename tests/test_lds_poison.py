@@ -149,13 +149,7 @@ def test_fmi_class_tasks_after_poison(poison):
     bwtSeedStrategyAllPosOneThread: fmi_task_wave with its per-launch dynamic LDS) give the same
     records after every poison pattern as before any, and AllPos + LAST give the batched search's
     (oracle-exact) SMEM sets per read."""
-    import ctypes as ct
     from genomicsbench_palisade_amd import fmi, lib
-    L = lib()
-    vp, i32, i64 = ct.c_void_p, ct.c_int32, ct.c_int64
-    L.gb_fmi_smem_allpos.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i64, vp, vp, vp]
-    L.gb_fmi_smem_onepos.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp]
-    L.gb_fmi_last_seeds.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, vp, vp]
     ref = gen.fmi_reference(300_000, seed=33, repeat_frac=0.2)
     codes, lens = gen.fmi_reads(ref, 600, read_len=151, seed=133, sub_rate=0.03, n_rate=0.002)
     n = len(lens)
@@ -173,21 +167,15 @@ def test_fmi_class_tasks_after_poison(poison):
         outs = []
         for which in ("allpos", "onepos", "last"):
             out = np.zeros(cap, fmi_util.SMEM_DTYPE)
-            nout, calls = ct.c_int64(), ct.c_int64()
             if which == "allpos":
-                st = L.gb_fmi_smem_allpos(idx.h, flat.ctypes.data, lens32.ctypes.data, offs.ctypes.data, n,
-                                          ones.ctypes.data, rid.ctypes.data, n, 19, out.ctypes.data, cap,
-                                          ct.byref(nout), None, ct.byref(calls))
+                st, nout, calls = idx.smem_allpos_raw(flat, lens32, offs, n, ones, rid, n, 19, out, cap, None)
             elif which == "onepos":
                 nxt = np.zeros(n, np.int16)
-                st = L.gb_fmi_smem_onepos(idx.h, flat.ctypes.data, lens32.ctypes.data, offs.ctypes.data, n,
-                                          qpos.ctypes.data, ones.ctypes.data, rid.ctypes.data, n, 19,
-                                          out.ctypes.data, cap, ct.byref(nout), nxt.ctypes.data, ct.byref(calls))
+                st, nout, calls = idx.smem_onepos_raw(flat, lens32, offs, n, qpos, ones, rid, n, 19, out, cap, nxt)
             else:
-                st = L.gb_fmi_last_seeds(idx.h, flat.ctypes.data, lens32.ctypes.data, offs.ctypes.data, n,
-                                         twenty.ctypes.data, 20, out.ctypes.data, cap, ct.byref(nout), ct.byref(calls))
-            assert st == 0, (which, L.gb_last_error())
-            outs.append((out[:nout.value].copy(), calls.value))
+                st, nout, calls = idx.last_seeds_raw(flat, lens32, offs, n, twenty, 20, out, cap)
+            assert st == 0, (which, lib().gb_last_error())
+            outs.append((out[:nout].copy(), calls))
         return outs
 
     try:
