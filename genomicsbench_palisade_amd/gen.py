@@ -896,3 +896,89 @@ def extd2_items(rng, shapes, params="map-ont", w=None, zdrop=None, end_bonus=Non
         seqs += [query, target]
         pos += qlen + tlen
     return Extd2Items(params, np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), items)
+
+
+# ---- poa: windows of noisy reads of a template ----
+
+POA_ALPHABET = b"ACGT"
+
+
+def poa_template(rng, length, kind="random", alphabet=POA_ALPHABET):
+    """A template of `length` bytes: "random" over the alphabet, "homopolymer" (runs of 3..12 of one base) or
+    "period" (a random unit of 2..4 bases repeated), the last two for ties."""
+    al = np.frombuffer(bytes(alphabet), np.uint8)
+    if kind == "random":
+        return al[rng.integers(0, len(al), length)].tobytes()
+    if kind == "period":
+        unit = al[rng.integers(0, len(al), int(rng.integers(2, 5)))]
+        return np.resize(unit, length).tobytes()
+    assert kind == "homopolymer", kind
+    out = []
+    while len(out) < length:
+        out += [int(al[rng.integers(0, len(al))])] * int(rng.integers(3, 13))
+    return bytes(out[:length])
+
+
+def poa_read(rng, template, sub=0.04, ins=0.04, dele=0.04, long_indel=0.0, long_len=(25, 40), start=0, end=None,
+             alphabet=POA_ALPHABET):
+    """A read of template[start:end] with substitution, insertion and deletion rates per base, and, at rate
+    long_indel per base, an insertion or a deletion of long_len[0] .. long_len[1] bases."""
+    al = np.frombuffer(bytes(alphabet), np.uint8)
+    t = np.frombuffer(bytes(template), np.uint8)[start:end]
+    out, i = [], 0
+    while i < len(t):
+        u = rng.random()
+        if u < long_indel:
+            k = int(rng.integers(long_len[0], long_len[1] + 1))
+            if rng.random() < 0.5:
+                out += [int(x) for x in al[rng.integers(0, len(al), k)]]
+            else:
+                i += k
+        elif u < long_indel + ins:
+            out.append(int(al[rng.integers(0, len(al))]))
+        elif u < long_indel + ins + dele:
+            i += 1
+        elif u < long_indel + ins + dele + sub:
+            others = al[al != t[i]]
+            out.append(int(others[rng.integers(0, len(others))]) if len(others) else int(t[i]))
+            i += 1
+        else:
+            out.append(int(t[i]))
+            i += 1
+    return bytes(out)
+
+
+def poa_window(rng, n_reads, length, err=0.12, long_indel=0.0, clip=0.0, kind="random", alphabet=POA_ALPHABET,
+               quals=False):
+    """A window: a template of `length` bytes and n_reads reads of it at a total error rate `err`, split evenly
+    over substitutions, insertions and deletions. With probability `clip` a read starts or ends up to a third of
+    the way inside the template. Returns (reads, quals or None); a quality string holds bytes 33 .. 73."""
+    t = poa_template(rng, length, kind, alphabet)
+    reads = []
+    for _ in range(n_reads):
+        start, end = 0, len(t)
+        if rng.random() < clip:
+            if rng.random() < 0.5:
+                start = int(rng.integers(0, len(t) // 3 + 1))
+            else:
+                end = len(t) - int(rng.integers(0, len(t) // 3 + 1))
+        reads.append(poa_read(rng, t, err / 3, err / 3, err / 3, long_indel, start=start, end=end, alphabet=alphabet))
+    qs = [rng.integers(33, 74, len(r)).astype(np.uint8).tobytes() for r in reads] if quals else None
+    return reads, qs
+
+
+def poa_windows(rng, n_windows, reads=(2, 12), length=(20, 300), err=0.12, long_indel=0.0, clip=0.0, kind="random",
+                alphabet=POA_ALPHABET):
+    """n_windows windows (lists of reads as bytes) with read counts and template lengths drawn from the closed
+    ranges `reads` and `length`."""
+    return [poa_window(rng, int(rng.integers(reads[0], reads[1] + 1)), int(rng.integers(length[0], length[1] + 1)),
+                       err, long_indel, clip, kind, alphabet)[0] for _ in range(n_windows)]
+
+
+def write_poa_file(path, windows):
+    """The poa benchmark's input: a header line per read, whose second character is '0' for the first read of a
+    window, then the read on a line of its own."""
+    with open(path, "w") as f:
+        for reads in windows:
+            for k, r in enumerate(reads):
+                f.write(f">{k}\n{bytes(r).decode()}\n")
