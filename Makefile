@@ -18,9 +18,9 @@ HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_c
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
 .PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize abea-sanitize abea-hmm-sanitize \
-        abea-viterbi-sanitize chain-extd2-sanitize poa-sanitize
+        abea-viterbi-sanitize chain-extd2-sanitize poa-sanitize kmer-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
-all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi $(BIN)/poa oracle tests/_build/fmi_class_driver \
+all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi $(BIN)/poa $(BIN)/kmer-cnt oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
 
 # the latency-bound DP loops schedule better for instruction-level parallelism (chain_rows -1.8 %,
@@ -67,6 +67,10 @@ $(BIN)/fmi: $(PKG)/drivers/fmi_main.cpp $(LIB)/libgb.so
 $(BIN)/poa: $(PKG)/drivers/poa_main.cpp $(LIB)/libgb.so include/gb_bsw_poa.h
 	@mkdir -p $(BIN)
 	$(HOSTCXX) $(HOSTFLAGS) -o $@ $< -L$(LIB) -lgb -Wl,-rpath,'$$ORIGIN/../lib'
+
+$(BIN)/kmer-cnt: $(PKG)/drivers/kmer_main.cpp $(LIB)/libgb.so include/gb_fmi_kmer.h
+	@mkdir -p $(BIN)
+	$(HOSTCXX) $(HOSTFLAGS) -o $@ $< -L$(LIB) -lgb -lz -Wl,-rpath,'$$ORIGIN/../lib'
 
 $(BIN)/phmm: $(PKG)/drivers/phmm_main.cpp $(LIB)/libgb.so
 	@mkdir -p $(BIN)
@@ -181,6 +185,15 @@ tests/_build/poa_host_check: tests/cpp/poa_host_check.cpp $(CSRC)/bsw_poa.hip $(
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_poa.hip \
+	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the same for the host path of gb_kmer_count and gb_kmer_index (GB_KMER_HOST=1). Not part of `all`.
+kmer-sanitize: tests/_build/kmer_host_check
+	tests/_build/kmer_host_check
+tests/_build/kmer_host_check: tests/cpp/kmer_host_check.cpp $(CSRC)/fmi_kmer.hip $(CSRC)/gb_common.cpp $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/fmi_kmer.hip \
 	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:

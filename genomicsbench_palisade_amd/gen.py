@@ -982,3 +982,40 @@ def write_poa_file(path, windows):
         for reads in windows:
             for k, r in enumerate(reads):
                 f.write(f">{k}\n{bytes(r).decode()}\n")
+
+
+# ---------------------------------------------------------------------------------------------------- kmer
+
+def kmer_reads(seed, genome_len, coverage, read_len_range=(1000, 20000), error_rate=0.05, repeats=0):
+    """Long reads over a random genome for the k-mer leg, as a list of u8 ACGT arrays: `repeats` copies of a 500-base
+    family are planted in the genome, reads start uniformly, have lengths drawn from the closed range, come from
+    either strand with equal chance and carry substitutions, insertions and deletions at error_rate in all. Reads
+    are drawn until their bases reach coverage * genome_len."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    genome = acgt[rng.integers(0, 4, int(genome_len))]
+    if repeats and genome_len > 2000:
+        family = acgt[rng.integers(0, 4, 500)]
+        for _ in range(int(repeats)):
+            at = int(rng.integers(0, genome_len - 500))
+            genome[at:at + 500] = family
+    lo, hi = int(read_len_range[0]), int(min(read_len_range[1], genome_len))
+    reads, total = [], 0
+    while total < coverage * genome_len:
+        n = int(rng.integers(lo, hi + 1))
+        at = int(rng.integers(0, genome_len - n + 1))
+        r = genome[at:at + n].copy()
+        if rng.random() < 0.5:
+            r = acgt[3 - np.searchsorted(acgt, r)][::-1].copy()
+        if error_rate > 0:
+            u = rng.random(n)
+            sub = u < error_rate / 3
+            r[sub] = acgt[rng.integers(0, 4, int(sub.sum()))]
+            dele = (u >= error_rate / 3) & (u < 2 * error_rate / 3)
+            ins = (u >= 2 * error_rate / 3) & (u < error_rate)
+            keep = np.repeat(np.arange(n), 1 + ins.astype(np.int64) - dele.astype(np.int64))
+            r = r[keep]
+            r = r[:hi] if len(r) >= lo else np.concatenate([r, acgt[rng.integers(0, 4, lo - len(r))]])
+        reads.append(np.ascontiguousarray(r))
+        total += len(r)
+    return reads
