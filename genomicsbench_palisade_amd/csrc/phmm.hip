@@ -62,11 +62,10 @@ constexpr int kPlanBuckets = 128;
 constexpr int kPlanCount = 8, kPlanCursor = kPlanCount + kPlanBuckets, kPlanTotal = kPlanCursor + kPlanBuckets;
 constexpr int kCountWords = kPlanTotal + 8;
 // behind the plan's total, the predictor's words: the gate's sample (testcases, predicted), testcases
-// predicted, confirmed and redone, and the redo launch's unit count and cursor
+// predicted, confirmed and redone
 constexpr int kPredSampled = kPlanTotal + 1, kPredSamplePred = kPlanTotal + 2, kPredPredicted = kPlanTotal + 3;
-constexpr int kPredConfirmed = kPlanTotal + 4, kPredRedone = kPlanTotal + 5, kRedoUnits = kPlanTotal + 6;
-constexpr int kRedoNext = kPlanTotal + 7;
-static_assert(kRedoNext < kCountWords, "counter words");
+constexpr int kPredConfirmed = kPlanTotal + 4, kPredRedone = kPlanTotal + 5;
+static_assert(kPredRedone < kCountWords, "counter words");
 constexpr int kMaxF64Parts = 8;
 constexpr int kM2M = ((127 * 128) >> 1) + 128;  // set_mm_prob indices for quals < 128
 
@@ -176,8 +175,8 @@ static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R)
   return G;
 }
 
-// The predictor's certificate (phmm_predict, phmm_verify). A predicted testcase skips the f32 pass and is
-// taken by the f64 pass; phmm_verify then needs the f64 result to prove that the f32 result, which nobody
+// The predictor's certificate (phmm_predict, verify_unit). A predicted testcase skips the f32 pass and is
+// taken by the f64 pass; verify_unit then needs the f64 result to prove that the f32 result, which nobody
 // computed, is below MIN_ACCEPTED. Both results are sums over the same alignment paths of products of
 // table entries, times INITIAL_CONSTANT / haplen: f32 of the f32 tables' entries with f32 roundings, f64
 // of the f64 tables'. A path visits at most R + C cells and takes at most two entries per cell (a
@@ -196,7 +195,7 @@ static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R)
 // haplotype of C columns. The pack certifies a read (kMayPredict in its first quality byte, whose bit 7
 // no kernel reads) when cert_K(R, kMaxHaplen) <= kCertMax: K grows with C, so the flag holds for every
 // haplotype the read meets. log(rho), rounded up to f32, follows the read's five byte rows in the pool, and
-// phmm_verify computes the testcase's own K from it.
+// verify_unit computes the testcase's own K from it.
 constexpr double kCertMax = 2.0;
 constexpr uint8_t kMayPredict = 0x80;
 // CertTab: per quality value the largest f32 / f64 ratio of the entries a row takes with it (+inf for an
@@ -249,6 +248,18 @@ struct DevTab {
   const T *ph2pr, *one_minus, *div3, *m2m;
   T init_const;
 };
+
+// the tables of upload_tables' blob at `base`
+template <typename T>
+__host__ __device__ inline DevTab<T> dev_tab(const T *base, T init_const) {
+  DevTab<T> t;
+  t.ph2pr = base;
+  t.one_minus = base + kQualTab;
+  t.div3 = base + 2 * kQualTab;
+  t.m2m = base + 3 * kQualTab;
+  t.init_const = init_const;
+  return t;
+}
 
 // Boundary record per column c (stripe above the current one): the two partial sums the first
 // row of the current stripe needs from the row above, already multiplied by THAT first row's
@@ -807,8 +818,8 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
   if (act) {
     d = descs[stk_tc[S.first + lane]];
     if constexpr (kF64Pass) act = force || raw_f[d.out_idx] < 1e-28f;  // MIN_ACCEPTED, pairhmm_common.h:16
-    // f32 pass: without the testcases phmm_predict took (sel = pred, 0); the redo launch: only those
-    // phmm_verify sent back (sel = redo, 1)
+    // f32 pass: without the testcases phmm_predict took (sel = pred, 0); the redo inside the f64 pass: only
+    // those verify_unit sent back (sel = redo, 1)
     else if (sel) act = sel[d.out_idx] == (uint8_t)sel_want;
   }
   const uint64_t am = __builtin_amdgcn_ballot_w64(act);
@@ -1223,6 +1234,48 @@ __device__ __forceinline__ void phmm_stack2(const Stack &S, const uint32_t *__re
   }
 }
 
+// cert_K as a call: inlined into the f64 pass's persistent loop, exp's polynomial constants are hoisted
+// out of that loop into 28 registers that live through the f64 sweeps, which have 21 to spare
+__device__ __attribute__((noinline)) double cert_K_call(double log_rho, int R, int C) { return cert_K(log_rho, R, C); }
+
+// After a unit of the f64 pass, by the wave that computed it (lane a: the stack's entry a, as in
+// phmm_stack): a predicted testcase whose f64 result proves the f32 result below MIN_ACCEPTED (cert_K) is
+// confirmed and counts, with all its cells, in the early exit's statistics (nok, okcells); every other
+// predicted testcase is marked in `redo` and counted in nre. A predicted testcase holds raw f32 0, so the
+// unit has just computed it. Returns whether the unit has a testcase to redo.
+__device__ __forceinline__ bool verify_unit(const Stack &S, int part, int parts, const uint32_t *__restrict__ stk_tc,
+                                            const TcDesc *__restrict__ descs, const uint8_t *__restrict__ pool,
+                                            const uint8_t *__restrict__ pred, const double *rd, uint8_t *redo,
+                                            int &nok, int &nre, unsigned long long &okcells) {
+  const int lane = threadIdx.x;
+  bool act = lane < (int)S.count;
+  if (parts > 1) act = act && lane >= part * (int)S.count / parts && lane < (part + 1) * (int)S.count / parts;
+  bool ok = false, re = false;
+  unsigned long long cells = 0;
+  if (act) {
+    const TcDesc d = descs[stk_tc[S.first + lane]];
+    if (pred[d.out_idx]) {
+      const int R = (int)(d.dims & 0xffff), C = (int)(d.dims >> 16);
+      const uint8_t *lp = pool + d.read_off + 5 * (size_t)R;  // the read's log(rho), unaligned
+      const uint32_t lb = (uint32_t)lp[0] | (uint32_t)lp[1] << 8 | (uint32_t)lp[2] << 16 | (uint32_t)lp[3] << 24;
+      const double K = cert_K_call((double)__builtin_bit_cast(float, lb), R, C);
+      ok = rd[d.out_idx] * 0x1p-900 * K + 4e-35 < (double)1e-28f;
+      re = !ok;
+      if (ok) cells = (unsigned long long)R * (unsigned long long)C;
+      else redo[d.out_idx] = 1;
+    }
+  }
+  const uint64_t okm = __builtin_amdgcn_ballot_w64(ok), rem = __builtin_amdgcn_ballot_w64(re);
+  if (okm) {
+    for (int o = 32; o >= 1; o >>= 1) cells += __shfl_xor(cells, o);
+    okcells += (unsigned long long)__builtin_amdgcn_readfirstlane((int)(cells & 0xffffffffu)) |
+               (unsigned long long)__builtin_amdgcn_readfirstlane((int)(cells >> 32)) << 32;
+    nok += __builtin_popcountll(okm);
+  }
+  nre += __builtin_popcountll(rem);
+  return rem != 0;
+}
+
 // W: the waves per SIMD the register allocation is held to (0: the compiler's own choice)
 template <int W>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8))) void phmm_forward2(
@@ -1245,36 +1298,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8
 // The LDS kernels' registers are held to the waves per SIMD their LDS allows (f32 8, f64 4). As built
 // by the Makefile (-O3 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp)
 // the f32 kernels take 59 and, with the exit, 64 registers without a spill (phmm_rolled's RowDesc,
-// fresh(), wave_sum_xor) and the f64 kernel 107 of 128; without the max-ilp scheduler 58 / 64 / 94.
-// kRedo: the f32 pass again over the stacks phmm_redo_plan listed (a persistent grid through
-// counter[kRedoNext]; no work, no stack), for the testcases marked in `sel`, without the early exit.
-template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false, bool kRedo = false>
+// fresh(), wave_sum_xor) and the f64 kernel 113 of 128 (107 before it took the f32 sweep in); without the
+// max-ilp scheduler the parent's were 58 / 64 / 94.
+// The f64 pass over the LDS stacks also settles the predictor's testcases (`sel` = pred, set when the
+// batch predicted): after each unit the wave confirms its predicted entries from the f64 results it has
+// just stored (verify_unit) and, where one is not confirmed, sweeps those entries in f32 at once (the
+// tables at `tabf`, into `raw_f`, sel = redo), in the same LDS; the SIMD's other waves hide that single
+// wave's latency. No list, and no wave waits on another.
+template <typename T, bool kF64Pass, bool kLong = false, bool kExit = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : (sizeof(T) == 4 ? 8 : 4), 8))) void phmm_forward(
     const Stack *__restrict__ stacks, int nstacks,
                                                     const uint32_t *__restrict__ stk_tc,
                                                     const TcDesc *__restrict__ descs,
                                                     const uint8_t *__restrict__ pool, DevTab<T> tab,
-                                                    T *__restrict__ raw_out, const float *__restrict__ raw_f,
+                                                    T *__restrict__ raw_out, const float *raw_f,
                                                     int *__restrict__ counter, int force, uint8_t *scratch,
                                                     size_t scratch_stride, const uint32_t *__restrict__ units,
-                                                    const uint8_t *__restrict__ sel, int sel_want) {
+                                                    const uint8_t *__restrict__ sel, int sel_want,
+                                                    const float *tabf, uint8_t *redo) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   uint8_t *rec = kLong ? scratch + (size_t)blockIdx.x * scratch_stride : smem_raw;
   const bool roll = (force >> 16) & 1;  // the LDS stacks' rolled sweep (phmm_rolled; GB_PHMM_ROLL)
-  if constexpr (kRedo) {
-    const int nwork = __builtin_amdgcn_readfirstlane(counter[kRedoUnits]);
-    while (true) {
-      int k = 0;
-      if (threadIdx.x == 0) k = atomicAdd(counter + kRedoNext, 1);
-      k = __builtin_amdgcn_readfirstlane(__shfl(k, 0));
-      if (k >= nwork) break;
-      k = __builtin_amdgcn_readfirstlane((int)units[k]);
-      phmm_stack<T, false, false, true>(stacks[k], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1, nullptr,
-                                        roll, sel, sel_want);
-      __syncthreads();
-    }
-  } else if constexpr (kF64Pass || kLong) {
+  if constexpr (kF64Pass || kLong) {
     int done = 0;
+    // the predictor's totals of this wave (wave-uniform): confirmed, their cells, redone
+    int nok = 0, nre = 0;
+    unsigned long long okcells = 0;
     int *next = counter + (kLong ? (kF64Pass ? 3 : 2) : 1);
     // f64 pass over the LDS stacks: `parts` work units per stack (the top byte of `force`), so a job
     // of few stacks per worker balances its fallback work finer
@@ -1287,11 +1336,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLong ? 1 : 
       k = __builtin_amdgcn_readfirstlane(__shfl(k, 0));
       if (k >= nwork) break;
       if (units) k = __builtin_amdgcn_readfirstlane((int)units[k]);
-      done += phmm_stack<T, kF64Pass, false, !kLong>(stacks[k / parts], stk_tc, descs, pool, tab, raw_out, raw_f,
-                                                     (force & 0xFF) != 0, rec, k % parts, parts, nullptr, roll);
+      const int nf = phmm_stack<T, kF64Pass, false, !kLong>(stacks[k / parts], stk_tc, descs, pool, tab, raw_out, raw_f,
+                                                            (force & 0xFF) != 0, rec, k % parts, parts, nullptr, roll);
+      done += nf;
       __syncthreads();  // the next stack re-initialises the records
+      if constexpr (kF64Pass && !kLong) {
+        // (the barrier above has also waited for the unit's result stores: verify_unit reads them back)
+        if (sel && nf) {
+          if (verify_unit(stacks[k / parts], k % parts, parts, stk_tc, descs, pool, sel, raw_out, redo, nok, nre,
+                          okcells)) {
+            __syncthreads();
+            phmm_stack<float, false, false, true>(stacks[k / parts], stk_tc, descs, pool, dev_tab(tabf, 0x1p120f),
+                                                  const_cast<float *>(raw_f), nullptr, false, rec, k % parts, parts,
+                                                  nullptr, roll, redo, 1);
+            __syncthreads();
+          }
+        }
+      }
     }
-    if (kF64Pass && threadIdx.x == 0 && done) atomicAdd(counter, done);
+    if (kF64Pass && threadIdx.x == 0) {
+      if (done) atomicAdd(counter, done);
+      if (nok) {
+        atomicAdd(counter + kPredConfirmed, nok);
+        atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4), (unsigned long long)nok);
+        atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4) + 1, okcells);
+      }
+      if (nre) atomicAdd(counter + kPredRedone, nre);
+    }
   } else {
     phmm_stack<T, false, kExit, true>(stacks[blockIdx.x], stk_tc, descs, pool, tab, raw_out, nullptr, false, rec, 0, 1,
                                       reinterpret_cast<unsigned long long *>(counter + 4), roll, sel, sel_want);
@@ -1369,10 +1440,10 @@ __global__ __launch_bounds__(256) void f64_plan_order(int nunits, const uint8_t 
 // 1.4 / 2.5 / 3.9 (base quality below 14 / below 28 / from 28) and an overhang of n rows 4.5 + (n - 1), in
 // units of 0.01 log10; predicted when the cost exceeds -log10(MIN_ACCEPTED * 2^-120 * C) + kPredMargin.
 // A predicted testcase gets pred = 1 and raw f32 = 0: the f32 pass compacts it out of its stack and the
-// f64 pass takes it. The estimate is not a bound. phmm_verify confirms a prediction from the f64 result
-// and the read's certificate (cert_K: f32 <= K * f64 * 2^-900 + 4e-35, so f32 < MIN_ACCEPTED is
-// proved); what it cannot confirm is marked `redo`, and a second launch of the f32 kernel computes those
-// testcases' f32 results after all (phmm_redo_plan lists their stacks), as if they had never been
+// f64 pass takes it. The estimate is not a bound. The f64 pass confirms a prediction from the f64 result
+// and the read's certificate (verify_unit; cert_K: f32 <= K * f64 * 2^-900 + 4e-35, so f32 < MIN_ACCEPTED
+// is proved); what it cannot confirm is marked `redo`, and the wave that computed the unit sweeps those
+// testcases in f32 after all, inside the f64 pass's grid, as if they had never been
 // predicted. Only certified reads are predicted.
 // The kernel: a wave per stack. The haplotype's columns become four bit planes in LDS (base A / C / T /
 // G, each also set for N and outside the haplotype, whose rows cost their overhang), column c at bit c + 64. Per testcase, 64 rows at a time, the
@@ -1389,7 +1460,7 @@ __global__ __launch_bounds__(256) void f64_plan_order(int nunits, const uint8_t 
 // predictions and nothing else written, read back at the synchronisation the fill ends with. With fewer
 // than 1 in kGateDen predicted the gate is closed and gb_phmm_batch_run launches exactly what it launched
 // without the predictor: a batch that does not fall back pays nothing per step. A one-shot call
-// (gb_phmm_compute) pays the sample at every fill and the redo launch's latency at every step, about
+// (gb_phmm_compute) pays the sample at every fill and the redone testcases' latency at every step, about
 // 0.5 ms, so there the predictor is used from kPredMinCells cells a call only; a batch made by
 // gb_phmm_batch_create is sampled once and run many times, and is predicted at any size.
 // kPredOpen: everything with no gate (GB_PHMM_PREDICT=open), kPredAll: every certified testcase.
@@ -1454,17 +1525,30 @@ __global__ __launch_bounds__(64) void phmm_predict(const Stack *__restrict__ sta
       const int R = (int)(d.dims & 0xffff);
       const uint8_t *rb = pool + d.read_off;
       if (!(rb[R] & kMayPredict) || R > kPredMaxRows) continue;
-      int best = 1 << 30;
+      // only `best > thr` leaves the kernel, and every term of a diagonal's cost is non-negative: a chunk
+      // with no diagonal at or below thr after some rows is left (`alive`, wave-uniform, looked at after every
+      // 64 rows that have rows below them; both overhangs are known before row 0 and count from there), and
+      // a group that ends with a diagonal at or below thr decides "not predicted" for the testcase
+      bool low = false;
       if (mode != kPredAll) {
         const int dhi = C - R + kPredPad;
-        for (int g0 = 0; g0 - kPredPad <= dhi; g0 += 64 * kPredChunks) {
+        for (int g0 = 0; g0 - kPredPad <= dhi && !low; g0 += 64 * kPredChunks) {
           const int nch = min(kPredChunks, (dhi + kPredPad - g0) / 64 + 1);
           const int e0 = 1 + g0 + lane;  // the lane's diagonal of chunk 0, + 64: its bit at row 0
           const uint32_t sh = (uint32_t)e0 & 31u;
           const uint32_t *w0 = &plane[0][e0 >> 5];
           uint32_t n0[kPredChunks], n1[kPredChunks], n2[kPredChunks];
           for (int c = 0; c < kPredChunks; c++) n0[c] = n1[c] = n2[c] = 0;
-          for (int r64 = 0; r64 < R; r64 += 64) {
+          // chunk c's diagonal of this lane at or below thr, with the rows counted so far
+          auto at_or_below = [&](int c) {
+            const int dg = g0 + 64 * c + lane - kPredPad;
+            const int n_lo = min(R, max(0, -dg)), n_hi = min(R - n_lo, max(0, R + dg - C));
+            const int cost = 140 * (int)n0[c] + 250 * (int)n1[c] + 390 * (int)n2[c] + pred_overhang(n_lo) +
+                             pred_overhang(n_hi);
+            return dg <= dhi && cost <= thr;
+          };
+          uint32_t alive = (1u << nch) - 1u;
+          for (int r64 = 0; r64 < R && alive; r64 += 64) {
             const int row = r64 + lane;
             const bool in = row < R;
             const uint32_t rm = in ? rb[row] : 0u, qv = in ? (uint32_t)(rb[R + row] & 127) : 0u;
@@ -1479,7 +1563,7 @@ __global__ __launch_bounds__(64) void phmm_predict(const Stack *__restrict__ sta
             const bool two = r64 + 32 < R;
 #pragma unroll
             for (int c = 0; c < kPredChunks; c++) {
-              if (c < nch) {
+              if ((alive >> c) & 1u) {
                 uint32_t ha[4], hb[4];
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
@@ -1502,21 +1586,20 @@ __global__ __launch_bounds__(64) void phmm_predict(const Stack *__restrict__ sta
                 }
               }
             }
-          }
+            if (r64 + 64 < R) {
 #pragma unroll
-          for (int c = 0; c < kPredChunks; c++) {
-            const int dg = g0 + 64 * c + lane - kPredPad;
-            if (c < nch && dg <= dhi) {
-              const int n_lo = min(R, max(0, -dg)), n_hi = min(R - n_lo, max(0, R + dg - C));
-              const int cost = 140 * (int)n0[c] + 250 * (int)n1[c] + 390 * (int)n2[c] + pred_overhang(n_lo) +
-                               pred_overhang(n_hi);
-              best = min(best, cost);
+              for (int c = 0; c < kPredChunks; c++)
+                if (((alive >> c) & 1u) && !__builtin_amdgcn_ballot_w64(at_or_below(c))) alive &= ~(1u << c);
             }
           }
+          // a chunk that stayed alive has swept all rows: its costs are final (a dead one's are above thr)
+#pragma unroll
+          for (int c = 0; c < kPredChunks; c++)
+            if ((alive >> c) & 1u) low = low || at_or_below(c);
+          low = __builtin_amdgcn_ballot_w64(low) != 0;
         }
-        best = __builtin_amdgcn_readlane(gb::scan_min<(1 << 30)>(best), 63);
       }
-      if (best > thr) {
+      if (!low) {
         npred++;
         if (lane == 0 && mode != kPredSample) {
           pred[d.out_idx] = 1;
@@ -1532,68 +1615,13 @@ __global__ __launch_bounds__(64) void phmm_predict(const Stack *__restrict__ sta
   }
 }
 
-// After the f64 pass, a thread per testcase: a predicted testcase whose f64 result proves the f32 result
-// below MIN_ACCEPTED (cert_K) is confirmed and counts, with all its cells, in the early exit's statistics;
-// every other predicted testcase is marked for the redo launch.
-__global__ __launch_bounds__(256) void phmm_verify(const TcDesc *__restrict__ descs, int n,
-                                                   const uint8_t *__restrict__ pool,
-                                                   const uint8_t *__restrict__ pred, const double *__restrict__ rd,
-                                                   uint8_t *__restrict__ redo, int *__restrict__ counter) {
-  if (__builtin_amdgcn_readfirstlane(counter[kPredPredicted]) == 0) return;
-  int nok = 0, nre = 0;
-  unsigned long long cells = 0;
-  // a small grid strides over the testcases: the counters take one set of atomics per wave
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
-    if (!pred[k]) continue;
-    const TcDesc d = descs[k];
-    const int R = (int)(d.dims & 0xffff), C = (int)(d.dims >> 16);
-    const uint8_t *lp = pool + d.read_off + 5 * (size_t)R;  // the read's log(rho), unaligned
-    const uint32_t lb = (uint32_t)lp[0] | (uint32_t)lp[1] << 8 | (uint32_t)lp[2] << 16 | (uint32_t)lp[3] << 24;
-    const double K = cert_K((double)__builtin_bit_cast(float, lb), R, C);
-    if (rd[k] * 0x1p-900 * K + 4e-35 < (double)1e-28f) {
-      cells += (unsigned long long)R * (unsigned long long)C;
-      nok++;
-    } else {
-      redo[k] = 1;
-      nre++;
-    }
-  }
-  for (int o = 32; o >= 1; o >>= 1) {
-    cells += __shfl_xor(cells, o);
-    nok += __shfl_xor(nok, o);
-    nre += __shfl_xor(nre, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (nok) {
-      atomicAdd(counter + kPredConfirmed, nok);
-      atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4), (unsigned long long)nok);
-      atomicAdd(reinterpret_cast<unsigned long long *>(counter + 4) + 1, cells);
-    }
-    if (nre) atomicAdd(counter + kPredRedone, nre);
-  }
-}
-
-// The stacks with a testcase to redo, in any order (a testcase's result does not depend on its stack).
-__global__ __launch_bounds__(256) void phmm_redo_plan(const Stack *__restrict__ stacks, int nstacks,
-                                                      const uint32_t *__restrict__ stk_tc,
-                                                      const uint8_t *__restrict__ redo, int *__restrict__ counter,
-                                                      uint32_t *__restrict__ units) {
-  if (__builtin_amdgcn_readfirstlane(counter[kPredRedone]) == 0) return;
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= nstacks) return;
-  const Stack S = stacks[k];
-  bool any = false;
-  for (uint32_t a = 0; a < S.count && !any; a++) any = redo[stk_tc[S.first + a]] != 0;  // out_idx = testcase index
-  if (any) units[atomicAdd(counter + kRedoUnits, 1)] = (uint32_t)k;
-}
-
 // gb_phmm_init's warm-up launch (no work)
 __global__ void phmm_warm(int *count) {
   if (threadIdx.x == 0 && blockIdx.x == 0) count[3] = 0;
 }
 
 // Device log10 epilogue (IntelPairHmmCSource.cpp:73-79); the host path recomputes it bit-exactly.
-// After a redo launch (`redo` set): a redone testcase whose f32 result passes MIN_ACCEPTED is answered from
+// After a predicted run (`redo` set): a redone testcase whose f32 result passes MIN_ACCEPTED is answered from
 // f32, as in the reference: its f64 result reads 0 like that of any testcase that never fell back, and it
 // leaves the count of fallbacks (counter[0], gb_phmm_batch_stats).
 __global__ void phmm_finalize(const float *__restrict__ rf, double *__restrict__ rd,
@@ -1675,23 +1703,11 @@ int get_device_tables(DeviceTables **out) {
   st = upload_tables(*g_hd, &t->d);
   if (st) return st;
   for (auto fn : {(const void *)phmm_forward<float, false>, (const void *)phmm_forward<float, false, false, true>,
-                  (const void *)phmm_forward<double, true>,
-                  (const void *)phmm_forward<float, false, false, false, true>, (const void *)phmm_forward2<0>, (const void *)phmm_forward2<6>, (const void *)phmm_forward2<8>})
+                  (const void *)phmm_forward<double, true>, (const void *)phmm_forward2<0>, (const void *)phmm_forward2<6>, (const void *)phmm_forward2<8>})
     GB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   g_dev[dev] = t;
   *out = t;
   return GB_OK;
-}
-
-template <typename T>
-DevTab<T> dev_tab(const T *base, T init_const) {
-  DevTab<T> t;
-  t.ph2pr = base;
-  t.one_minus = base + kQualTab;
-  t.div3 = base + 2 * kQualTab;
-  t.m2m = base + 3 * kQualTab;
-  t.init_const = init_const;
-  return t;
 }
 
 // Deduplication keys: the caller shares read/haplotype buffers across the R x H cross product
@@ -1763,7 +1779,7 @@ struct gb_phmm_batch {
   bool gate_open = false; // batch_fill's sample: enough of the batch is predicted for the predictor to run
   int gate_n = 0, gate_pred = 0;  // the sample's testcases and predictions
   uint8_t *d_pred = nullptr;  // per testcase: predicted (skips the f32 pass), and behind it d_redo
-  uint8_t *d_redo = nullptr;  // per testcase: prediction not confirmed, f32 result computed by the redo launch
+  uint8_t *d_redo = nullptr;  // per testcase: prediction not confirmed, f32 result computed after all, inside the f64 pass
   size_t pred_bytes = 0;      // of d_rd, d_pred and d_redo together (adjacent in the arena)
   // host scratch of the fills (grow-only, host_reserve)
   std::vector<uint32_t> hid;
@@ -2501,6 +2517,7 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
     // the fallback predictor, on the exit's switch too (GB_PHMM_EXIT=0 keeps every raw f32), when the
     // fill's sample opened the gate; the f32 pass then leaves the predicted testcases out
     const uint8_t *skip = predict ? b->d_pred : nullptr;
+    // its f64 pass confirms the predictions, or computes the f32 result after all (verify_unit)
     if (predict) {
       const int pg = std::min(ns, b->cus * 16);
       hipLaunchKernelGGL(phmm_predict, dim3(pg), dim3(kWave), 0, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
@@ -2518,13 +2535,13 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
         hipLaunchKernelGGL(f32k, dim3(ns), dim3(kWave), lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                            b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr,
                            b->d_count, b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr,
-                           skip, 0);
+                           skip, 0, (const float *)nullptr, (uint8_t *)nullptr);
       }
       if (nl > 0)
         hipLaunchKernelGGL((phmm_forward<float, false, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
                            nl, b->d_stk_tc, b->d_desc, b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf,
                            (const float *)nullptr, b->d_count, 0, b->d_scratch, b->scratch_stride,
-                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0);
+                           (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0, (const float *)nullptr, (uint8_t *)nullptr);
       GB_HIP(hipGetLastError());
     }
     GB_HIP(hipEventRecord(b->ev[1], b->stream));
@@ -2543,29 +2560,14 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
                          b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd, (const float *)b->d_rf,
                          b->d_count, (b->force_f64 ? 1 : 0) | (b->f64_parts << 8) | (b->roll ? 1 << 16 : 0),
                          (uint8_t *)nullptr, (size_t)0,
-                         b->f64_plan ? (const uint32_t *)b->d_units : nullptr, (const uint8_t *)nullptr, 0);
+                         b->f64_plan ? (const uint32_t *)b->d_units : nullptr, skip, 0,
+                         (const float *)t->f, predict ? b->d_redo : nullptr);
     }
     if (nl > 0)
       hipLaunchKernelGGL((phmm_forward<double, true, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
                          nl, b->d_stk_tc, b->d_desc, b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd,
                          (const float *)b->d_rf, b->d_count, b->force_f64 ? 1 : 0, b->d_scratch, b->scratch_stride,
-                         (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0);
-    if (predict) {
-      // confirm the predictions from the f64 results; the f32 pass again for those not confirmed (its
-      // grid finds no work when there are none), over d_units, which the f64 pass is done with
-      const dim3 sg((unsigned)((ns + 255) / 256)), tb(256);
-      const dim3 vg((unsigned)std::min((n + 255) / 256, b->cus));
-      hipLaunchKernelGGL(phmm_verify, vg, tb, 0, b->stream, (const TcDesc *)b->d_desc, n,
-                         (const uint8_t *)b->d_pool.get(), (const uint8_t *)b->d_pred,
-                         (const double *)b->d_rd, b->d_redo, b->d_count);
-      hipLaunchKernelGGL(phmm_redo_plan, sg, tb, 0, b->stream, (const Stack *)b->d_stacks, ns,
-                         (const uint32_t *)b->d_stk_tc, (const uint8_t *)b->d_redo, b->d_count, b->d_units);
-      hipLaunchKernelGGL((phmm_forward<float, false, false, false, true>), dim3(std::min(ns, b->cus * 8)), dim3(kWave),
-                         lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc, b->d_pool,
-                         dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr, b->d_count,
-                         b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)b->d_units,
-                         (const uint8_t *)b->d_redo, 1);
-    }
+                         (const uint32_t *)nullptr, (const uint8_t *)nullptr, 0, (const float *)nullptr, (uint8_t *)nullptr);
     GB_HIP(hipGetLastError());
     GB_HIP(hipEventRecord(b->ev[2], b->stream));
     hipLaunchKernelGGL(phmm_finalize, dim3((n + 255) / 256), dim3(256), 0, b->stream, b->d_rf, b->d_rd,
