@@ -18,7 +18,7 @@ HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_c
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
 .PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize abea-sanitize abea-hmm-sanitize \
-        abea-viterbi-sanitize chain-extd2-sanitize poa-sanitize kmer-sanitize
+        abea-viterbi-sanitize chain-extd2-sanitize poa-sanitize kmer-sanitize dbg-sanitize
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi $(BIN)/poa $(BIN)/kmer-cnt oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -194,6 +194,15 @@ tests/_build/kmer_host_check: tests/cpp/kmer_host_check.cpp $(CSRC)/fmi_kmer.hip
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/fmi_kmer.hip \
+	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+
+# the same for the host path of gb_dbg_assemble (GB_DBG_HOST=1). Not part of `all`.
+dbg-sanitize: tests/_build/dbg_host_check
+	tests/_build/dbg_host_check
+tests/_build/dbg_host_check: tests/cpp/dbg_host_check.cpp $(CSRC)/fmi_dbg.hip $(CSRC)/gb_common.cpp $(HDRS)
+	@mkdir -p tests/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/fmi_dbg.hip \
 	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 
 oracle:

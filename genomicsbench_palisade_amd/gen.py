@@ -1019,3 +1019,45 @@ def kmer_reads(seed, genome_len, coverage, read_len_range=(1000, 20000), error_r
         reads.append(np.ascontiguousarray(r))
         total += len(r)
     return reads
+
+
+# ----------------------------------------------------------------------------------------------------- dbg
+
+def dbg_regions(seed, n_regions, region=1500, n_reads=300, read_len=150, sub_rate=0.01, n_rate=0.002, low_qual=0.03,
+                repeat_every=0, qc_fail=0.01):
+    """Overlapping assembly regions over a random genome for the dbg leg, shaped as the reference's driver shapes
+    them: region i assembles [a, a + region) with a = region + i * region / 2, its reference is the 3 * region bases
+    around it and its reads are those of the sorted pool that overlap it, about n_reads each. Reads of read_len bases
+    carry substitutions, a few 'N's, qualities of 30..40 with a fraction low_qual below 20, and the QC-fail flag at
+    rate qc_fail. Every repeat_every-th region (0: none) gets a 24-base unit planted twice, 40 bases apart, so that
+    its graph is cyclic at k = 15 and 20. Returns (regions, reads) as dbg.pack takes them: regions of
+    (reference u8, ref_start, read_first, read_last), reads of (sequence u8, qualities u8, flag)."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    shift = region // 2
+    length = 3 * region + shift * (int(n_regions) - 1)
+    genome = acgt[rng.integers(0, 4, length)]
+    starts = [region + i * shift for i in range(int(n_regions))]
+    if repeat_every:
+        for a in starts[::int(repeat_every)]:
+            at = a + int(rng.integers(0, shift - 100))
+            genome[at + 40:at + 64] = genome[at:at + 24]
+    total = max(1, int(n_reads * length / (region + read_len)))
+    pos = np.sort(rng.integers(0, length - read_len + 1, total))
+    reads = []
+    for p in pos:
+        s = genome[p:p + read_len].copy()
+        u = rng.random(read_len)
+        sub = u < sub_rate
+        s[sub] = acgt[rng.integers(0, 4, int(sub.sum()))]
+        s[(u >= sub_rate) & (u < sub_rate + n_rate)] = ord("N")
+        q = rng.integers(30, 41, read_len).astype(np.uint8)
+        low = rng.random(read_len) < low_qual
+        q[low] = rng.integers(2, 20, int(low.sum()))
+        reads.append((s, q, 512 if rng.random() < qc_fail else 0))
+    regions = []
+    for a in starts:
+        first = int(np.searchsorted(pos + read_len, a, side="right"))
+        last = int(np.searchsorted(pos, a + region, side="left"))
+        regions.append((genome[a - region:a + 2 * region].copy(), a - region, first, max(first, last)))
+    return regions, reads
