@@ -17,8 +17,7 @@ HIP_SRCS := $(wildcard $(CSRC)/*.hip)
 HIP_OBJS := $(patsubst $(CSRC)/%.hip,$(LIB)/obj/%.o,$(HIP_SRCS)) $(LIB)/obj/gb_common.o
 HDRS := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h)
 
-.PHONY: all ref clean oracle mkchain-sanitize regs-sanitize matesw-sanitize hostutil-sanitize abea-sanitize abea-hmm-sanitize \
-        abea-viterbi-sanitize chain-extd2-sanitize poa-sanitize kmer-sanitize dbg-sanitize
+.PHONY: all ref clean oracle
 DROPINS := $(LIB)/libgkl_pairhmm_c.so $(LIB)/libgb_chain_dropin.so $(LIB)/libgb_bsw_dropin.so $(LIB)/libgb_fmi_dropin.so
 all: $(LIB)/libgb.so $(DROPINS) $(BIN)/phmm $(BIN)/chain $(BIN)/bsw $(BIN)/fmi $(BIN)/poa $(BIN)/kmer-cnt oracle tests/_build/fmi_class_driver \
      tests/_build/libdropin_bench.so tests/_build/liblds_poison.so tests/_build/devbuf_check
@@ -96,114 +95,37 @@ tests/_build/devbuf_check: tests/cpp/devbuf_check.cpp $(LIB)/libgb.so $(HDRS)
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -Wall -o $@ $< -L$(LIB) -lgb -Wl,-rpath,'$$ORIGIN/../../$(LIB)'
 
-# the host path of gb_bsw_seeds2chains under the address and undefined-behaviour sanitizers: a stand-alone
-# program (its own main, no device touched) built from the library's two source files it needs, and run.
-# Not part of `all`.
-mkchain-sanitize: tests/_build/mkchain_host_check
-	tests/_build/mkchain_host_check
-tests/_build/mkchain_host_check: tests/cpp/mkchain_host_check.cpp $(CSRC)/bsw_mkchain.hip $(CSRC)/gb_common.cpp $(HDRS)
+# Host code under the address and undefined-behaviour sanitizers: `make <name>-sanitize` builds the stand-alone
+# program tests/_build/<program> (its own main in tests/cpp/<program>.cpp, no device touched) from the library's
+# source files it needs plus the common one, and runs it. None is part of `all`.
+# $(1) name, $(2) program, $(3) the library's source files besides gb_common.cpp
+define SANITIZE_RULE
+.PHONY: $(1)-sanitize
+$(1)-sanitize: tests/_build/$(2)
+	tests/_build/$(2)
+tests/_build/$(2): tests/cpp/$(2).cpp $(addprefix $(CSRC)/,$(3)) $(CSRC)/gb_common.cpp $(HDRS)
 	@mkdir -p tests/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_mkchain.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for gb_bsw_finish_regs: its source file, the two it calls into (the packed reference and the
-# band rule) and the common one. The call runs on the host and the program touches no device. Not part of
-# `all`.
-REGS_CHECK_SRCS := $(CSRC)/bsw_regs.hip $(CSRC)/bsw_gencigar.hip $(CSRC)/bsw_global.hip $(CSRC)/gb_common.cpp
-regs-sanitize: tests/_build/regs_host_check
-	tests/_build/regs_host_check
-tests/_build/regs_host_check: tests/cpp/regs_host_check.cpp $(REGS_CHECK_SRCS) $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(REGS_CHECK_SRCS) \
-	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host bookkeeping of gb_bsw_mate_rescue: the rounds run over alignment results that the
-# program supplies from a table, so no device is touched. Not part of `all`.
-MATESW_CHECK_SRCS := $(CSRC)/bsw_matesw.hip $(CSRC)/bsw_local.hip $(CSRC)/bsw_gencigar.hip $(CSRC)/bsw_global.hip \
-                     $(CSRC)/gb_common.cpp
-matesw-sanitize: tests/_build/matesw_host_check
-	tests/_build/matesw_host_check
-tests/_build/matesw_host_check: tests/cpp/matesw_host_check.cpp $(MATESW_CHECK_SRCS) $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(MATESW_CHECK_SRCS) \
-	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the host utilities of gb_common.h (fork-join, thread count, per-thread workspaces, round-up) under the
-# same sanitizers: no HIP call is made. Not part of `all`.
-hostutil-sanitize: tests/_build/hostutil_check
-	tests/_build/hostutil_check
-tests/_build/hostutil_check: tests/cpp/hostutil_check.cpp $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/gb_common.cpp \
-	  $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_abea_align (GB_ABEA_HOST=1): its source file and the common one; no
-# device is touched. Not part of `all`.
-abea-sanitize: tests/_build/abea_host_check
-	tests/_build/abea_host_check
-tests/_build/abea_host_check: tests/cpp/abea_host_check.cpp $(CSRC)/bsw_abea.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_abea.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_abea_hmm_score (GB_ABEA_HOST=1). Not part of `all`.
-abea-hmm-sanitize: tests/_build/abea_hmm_host_check
-	tests/_build/abea_hmm_host_check
-tests/_build/abea_hmm_host_check: tests/cpp/abea_hmm_host_check.cpp $(CSRC)/bsw_abea_hmm.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_abea_hmm.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_abea_hmm_align (GB_ABEA_HOST=1). Not part of `all`.
-abea-viterbi-sanitize: tests/_build/abea_viterbi_host_check
-	tests/_build/abea_viterbi_host_check
-tests/_build/abea_viterbi_host_check: tests/cpp/abea_viterbi_host_check.cpp $(CSRC)/bsw_abea_viterbi.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_abea_viterbi.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_chain_extd2 (GB_CHAIN_EXTD2_HOST=1). Not part of `all`.
-chain-extd2-sanitize: tests/_build/chain_extd2_host_check
-	tests/_build/chain_extd2_host_check
-tests/_build/chain_extd2_host_check: tests/cpp/chain_extd2_host_check.cpp $(CSRC)/chain_extd2.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/chain_extd2.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_poa_align and gb_poa_consensus (GB_POA_HOST=1). Not part of `all`.
-poa-sanitize: tests/_build/poa_host_check
-	tests/_build/poa_host_check
-tests/_build/poa_host_check: tests/cpp/poa_host_check.cpp $(CSRC)/bsw_poa.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/bsw_poa.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_kmer_count and gb_kmer_index (GB_KMER_HOST=1). Not part of `all`.
-kmer-sanitize: tests/_build/kmer_host_check
-	tests/_build/kmer_host_check
-tests/_build/kmer_host_check: tests/cpp/kmer_host_check.cpp $(CSRC)/fmi_kmer.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/fmi_kmer.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
-
-# the same for the host path of gb_dbg_assemble (GB_DBG_HOST=1). Not part of `all`.
-dbg-sanitize: tests/_build/dbg_host_check
-	tests/_build/dbg_host_check
-tests/_build/dbg_host_check: tests/cpp/dbg_host_check.cpp $(CSRC)/fmi_dbg.hip $(CSRC)/gb_common.cpp $(HDRS)
-	@mkdir -p tests/_build
-	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(CSRC)/fmi_dbg.hip \
-	  $(CSRC)/gb_common.cpp $< -o $@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+	  -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer -x hip $(addprefix $(CSRC)/,$(3)) \
+	  $(CSRC)/gb_common.cpp $$< -o $$@ -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
+endef
+# the host paths of gb_bsw_seeds2chains, of gb_bsw_finish_regs (with the packed reference and the band rule it calls
+# into) and the host bookkeeping of gb_bsw_mate_rescue (the rounds run over alignment results from a table)
+$(eval $(call SANITIZE_RULE,mkchain,mkchain_host_check,bsw_mkchain.hip))
+$(eval $(call SANITIZE_RULE,regs,regs_host_check,bsw_regs.hip bsw_gencigar.hip bsw_global.hip))
+$(eval $(call SANITIZE_RULE,matesw,matesw_host_check,bsw_matesw.hip bsw_local.hip bsw_gencigar.hip bsw_global.hip))
+# the host utilities of gb_common.h: fork-join, thread count, per-thread workspaces, round-up, environment numbers
+# and switches, the chunk cutter
+$(eval $(call SANITIZE_RULE,hostutil,hostutil_check,))
+# the host paths (GB_*_HOST=1) of gb_abea_align, gb_abea_hmm_score, gb_abea_hmm_align, gb_chain_extd2, gb_poa_align and
+# gb_poa_consensus, gb_kmer_count and gb_kmer_index, gb_dbg_assemble
+$(eval $(call SANITIZE_RULE,abea,abea_host_check,bsw_abea.hip))
+$(eval $(call SANITIZE_RULE,abea-hmm,abea_hmm_host_check,bsw_abea_hmm.hip))
+$(eval $(call SANITIZE_RULE,abea-viterbi,abea_viterbi_host_check,bsw_abea_viterbi.hip))
+$(eval $(call SANITIZE_RULE,chain-extd2,chain_extd2_host_check,chain_extd2.hip))
+$(eval $(call SANITIZE_RULE,poa,poa_host_check,bsw_poa.hip))
+$(eval $(call SANITIZE_RULE,kmer,kmer_host_check,fmi_kmer.hip))
+$(eval $(call SANITIZE_RULE,dbg,dbg_host_check,fmi_dbg.hip))
 
 oracle:
 	$(MAKE) -s -C oracle all

@@ -478,10 +478,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void abea_fill_kernel(Args A) 
 static_assert(sizeof(gb_abea_stat) == 48, "gb_abea_stat is 12 words on the device");
 static_assert(sizeof(Model) == 12, "gb_abea_model is three floats");
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = 0, num_cus = 0;
-  gb::Stream stream;
-  gb::Event ev[2];
+struct Ws : gb::WsBase<2> {  // the calling thread's, through gb::get_ws
   gb::DevBuf<Model> d_model;
   gb::DevBuf<char> d_seqs;
   gb::DevBuf<float> d_events;
@@ -500,29 +497,12 @@ struct Ws {  // the calling thread's, through gb::thread_ws
   int64_t cells = 0, chunks = 0, waves = 0, ws_bytes = 0;
 };
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  int st = GB_ERR_HIP;
-  if (e == hipSuccess)
-    st = W->d_ctl.reserve(4);
-  else
-    gb::set_error("gb_abea_align workspace: %s", hipGetErrorString(e));
-  if (st) {
-    delete W;
-    return st;
-  }
-  *out = W;
-  return GB_OK;
-}
-
-struct Chunk {
-  int64_t lo, hi, bands, max_bands;  // reads [lo, hi), the sum and the maximum of n_events + n_kmers + 2
+struct Need {  // of a read: its bands, n_events + n_kmers + 2, a pair each in the chunk's pair region
+  int64_t bands;
+  int64_t bytes() const { return bands * (int64_t)sizeof(gb_abea_pair); }
+  void operator+=(const Need &o) { bands += o.bands; }
 };
+using Chunk = gb::Chunk<Need>;  // of the call's reads
 
 static inline int64_t read_bands(const gb_abea_read &r) { return (int64_t)r.n_events + (r.seq_len - kK + 1) + 2; }
 
@@ -560,39 +540,19 @@ static int validate(const gb_abea_model *model, const char *seqs, int64_t seq_by
   return GB_OK;
 }
 
-static int ws_budget(int64_t *bytes) {
-  *bytes = kDefaultWsBytes;
-  if (const char *e = getenv("GB_ABEA_WS_BYTES")) {
-    char *end = nullptr;
-    const long long v = strtoll(e, &end, 10);
-    GB_ARG(end != e && *end == 0 && v >= 1, "gb_abea_align: GB_ABEA_WS_BYTES = \"%s\" is not a byte count", e);
-    *bytes = v;
-  }
-  return GB_OK;
-}
-
-// Chunks of reads whose pair regions (8 bytes per band) fit region_bytes, one read at the least.
+// Chunks of reads whose pair regions (8 bytes per band) fit region_bytes, one read at the least: a read whose
+// region alone does not fit is a chunk of its own.
 static std::vector<Chunk> make_chunks(const gb_abea_read *reads, int64_t n_reads, int64_t region_bytes) {
   std::vector<Chunk> out;
-  const int64_t cap = std::max<int64_t>(1, region_bytes / (int64_t)sizeof(gb_abea_pair));
-  Chunk c{0, 0, 0, 0};
-  for (int64_t r = 0; r < n_reads; ++r) {
-    const int64_t nb = read_bands(reads[r]);
-    if (c.hi > c.lo && c.bands + nb > cap) {
-      out.push_back(c);
-      c = Chunk{r, r, 0, 0};
-    }
-    c.hi = r + 1, c.bands += nb, c.max_bands = std::max(c.max_bands, nb);
-  }
-  if (c.hi > c.lo) out.push_back(c);
+  (void)gb::cut_chunks(n_reads, region_bytes, [&](int64_t r) { return Need{read_bands(reads[r])}; }, &out);
   return out;
 }
 
 static int run_chunk_device(Ws *W, const gb_abea_read *reads, const Chunk &c, int64_t slice_bytes, gb_abea_stat *stats) {
   int st;
-  const int64_t m = c.hi - c.lo;
+  const int64_t m = c.last - c.first;
   if ((st = W->h_reads.reserve((size_t)m)) || (st = W->d_reads.reserve((size_t)m))) return st;
-  if ((st = W->h_pairs.reserve((size_t)c.bands)) || (st = W->d_pairs.reserve((size_t)c.bands))) return st;
+  if ((st = W->h_pairs.reserve((size_t)c.need.bands)) || (st = W->d_pairs.reserve((size_t)c.need.bands))) return st;
   if ((st = W->h_stats.reserve((size_t)m * 12)) || (st = W->d_stats.reserve((size_t)m * 12))) return st;
   if ((st = W->h_order.reserve((size_t)m)) || (st = W->d_order.reserve((size_t)m))) return st;
   // The reads longest first, cut into launches by length class (bands up to 4096, then per power of two): a
@@ -605,10 +565,10 @@ static int run_chunk_device(Ws *W, const gb_abea_read *reads, const Chunk &c, in
   std::vector<Launch> launches;
   int32_t *order = W->h_order;
   for (int64_t k = 0; k < m; ++k) order[k] = (int32_t)k;
-  std::stable_sort(order, order + m, [&](int32_t a, int32_t b) { return read_bands(reads[c.lo + a]) > read_bands(reads[c.lo + b]); });
+  std::stable_sort(order, order + m, [&](int32_t a, int32_t b) { return read_bands(reads[c.first + a]) > read_bands(reads[c.first + b]); });
   int64_t cur_class = -1, max_waves = 1, trace_words = 0;
   for (int64_t k = 0; k < m; ++k) {
-    const int64_t nb = read_bands(reads[c.lo + order[k]]);
+    const int64_t nb = read_bands(reads[c.first + order[k]]);
     int64_t cls = 4096;
     while (cls < nb) cls *= 2;
     if (cls != cur_class) {
@@ -628,11 +588,11 @@ static int run_chunk_device(Ws *W, const gb_abea_read *reads, const Chunk &c, in
   if ((st = W->d_cycles.reserve((size_t)max_waves * 2)) || (st = W->h_cycles.reserve((size_t)max_waves * 2))) return st;
   W->waves = std::max(W->waves, max_waves);
   W->ws_bytes = std::max<int64_t>(
-      W->ws_bytes, trace_words * (int64_t)sizeof(uint32_t) + c.bands * (int64_t)sizeof(gb_abea_pair));
+      W->ws_bytes, trace_words * (int64_t)sizeof(uint32_t) + c.need.bands * (int64_t)sizeof(gb_abea_pair));
   DRead *hr = W->h_reads;
   int64_t end = 0;
   for (int64_t k = 0; k < m; ++k) {
-    const gb_abea_read &s = reads[c.lo + k];
+    const gb_abea_read &s = reads[c.first + k];
     const Consts C = make_consts(s.n_events, s.seq_len - kK + 1);
     end += read_bands(s);
     hr[k] = DRead{s.seq_off, s.event_off, end, s.seq_len, s.n_events, s.scale, s.shift, C.lp_stay, C.lp_step};
@@ -658,7 +618,7 @@ static int run_chunk_device(Ws *W, const gb_abea_read *reads, const Chunk &c, in
   GB_HIP(hipMemcpyAsync(W->h_stats, W->d_stats, (size_t)m * 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, W->stream));
   GB_HIP(hipMemcpyAsync(W->h_cycles, W->d_cycles, (size_t)max_waves * 2 * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, W->stream));
-  GB_HIP(hipMemcpyAsync(W->h_pairs, W->d_pairs, (size_t)c.bands * sizeof(gb_abea_pair), hipMemcpyDeviceToHost,
+  GB_HIP(hipMemcpyAsync(W->h_pairs, W->d_pairs, (size_t)c.need.bands * sizeof(gb_abea_pair), hipMemcpyDeviceToHost,
                         W->stream));
   GB_HIP(hipStreamSynchronize(W->stream));
   float ms = 0.f;
@@ -668,9 +628,9 @@ static int run_chunk_device(Ws *W, const gb_abea_read *reads, const Chunk &c, in
   const double share = cf + cw > 0 ? cf / (cf + cw) : 1.0;
   W->fill_ms += (float)(ms * share), W->trace_ms += (float)(ms * (1.0 - share));
   for (int64_t k = 0; k < m; ++k) {
-    std::memcpy(&stats[c.lo + k], W->h_stats.get() + 12 * k, sizeof(gb_abea_stat));
-    finish_stat(&stats[c.lo + k]);
-    W->cells += stats[c.lo + k].fills;
+    std::memcpy(&stats[c.first + k], W->h_stats.get() + 12 * k, sizeof(gb_abea_stat));
+    finish_stat(&stats[c.first + k]);
+    W->cells += stats[c.first + k].fills;
   }
   return GB_OK;
 }
@@ -681,26 +641,16 @@ extern "C" {
 
 int gb_abea_align_timing(float *fill_ms, float *trace_ms, int64_t *cells) {
   GB_ARG(fill_ms && trace_ms && cells, "gb_abea_align_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbabea::Ws *W = gb::find_thread_ws<gbabea::Ws>(dev);
-  if (!W || !W->chunks) {
-    gb::set_error("gb_abea_align_timing: gb_abea_align has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbabea::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_abea_align_timing", "gb_abea_align", &W, &gbabea::Ws::chunks)) return st;
   *fill_ms = W->fill_ms, *trace_ms = W->trace_ms, *cells = W->cells;
   return GB_OK;
 }
 
 int gb_abea_align_plan(int64_t *chunks, int64_t *waves, int64_t *ws_bytes) {
   GB_ARG(chunks && waves && ws_bytes, "gb_abea_align_plan: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbabea::Ws *W = gb::find_thread_ws<gbabea::Ws>(dev);
-  if (!W || !W->chunks) {
-    gb::set_error("gb_abea_align_plan: gb_abea_align has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbabea::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_abea_align_plan", "gb_abea_align", &W, &gbabea::Ws::chunks)) return st;
   *chunks = W->chunks, *waves = W->waves, *ws_bytes = W->ws_bytes;
   return GB_OK;
 }
@@ -717,17 +667,16 @@ int gb_abea_align(const gb_abea_model *model, const char *seqs, int64_t seq_byte
   pair_off[0] = 0;
   if (n_reads == 0) return GB_OK;
   int64_t budget = 0;
-  if ((st = ws_budget(&budget))) return st;
+  if ((st = gb::env_number(who, "GB_ABEA_WS_BYTES", 1, INT64_MAX, kDefaultWsBytes, &budget))) return st;
   const std::vector<Chunk> chunks = make_chunks(reads, n_reads, budget / 2);
-  const char *he = getenv("GB_ABEA_HOST");
-  const bool host = he && *he == '1';
+  const bool host = gb::env_flag("GB_ABEA_HOST");
 
   // the pairs of all chunks in their final, packed order; they reach pairs[] only once the need is known
   std::vector<gb_abea_pair> packed;
   int64_t used = 0;
   auto pack = [&](const Chunk &c, const gb_abea_pair *region) {
     int64_t end = 0;
-    for (int64_t r = c.lo; r < c.hi; ++r) {
+    for (int64_t r = c.first; r < c.last; ++r) {
       end += read_bands(reads[r]);
       const int64_t n = stats[r].n_raw;
       pair_off[r] = used;
@@ -741,18 +690,18 @@ int gb_abea_align(const gb_abea_model *model, const char *seqs, int64_t seq_byte
       if ((st = gb::thread_count(who, "GB_ABEA_THREADS", &nth))) return st;
       std::vector<gb_abea_pair> region;
       for (const Chunk &c : chunks) {
-        region.resize((size_t)c.bands);
-        std::vector<int64_t> ends((size_t)(c.hi - c.lo));
+        region.resize((size_t)c.need.bands);
+        std::vector<int64_t> ends((size_t)(c.last - c.first));
         int64_t end = 0;
-        for (int64_t r = c.lo; r < c.hi; ++r) ends[(size_t)(r - c.lo)] = end += read_bands(reads[r]);
-        std::atomic<int64_t> next{c.lo};
-        const int use = (int)std::min<int64_t>(nth, c.hi - c.lo);
+        for (int64_t r = c.first; r < c.last; ++r) ends[(size_t)(r - c.first)] = end += read_bands(reads[r]);
+        std::atomic<int64_t> next{c.first};
+        const int use = (int)std::min<int64_t>(nth, c.last - c.first);
         if ((st = gb::parallel(who, use, [&](int) {
                HostScratch S;
-               for (int64_t r; (r = next.fetch_add(1)) < c.hi;) {
+               for (int64_t r; (r = next.fetch_add(1)) < c.last;) {
                  const gb_abea_read &s = reads[r];
                  host_align(model, seqs + s.seq_off, s.seq_len, event_mean + s.event_off, s.n_events, s.scale, s.shift,
-                            region.data(), ends[(size_t)(r - c.lo)], &stats[r], &S);
+                            region.data(), ends[(size_t)(r - c.first)], &stats[r], &S);
                }
              })))
           return st;
@@ -762,7 +711,7 @@ int gb_abea_align(const gb_abea_model *model, const char *seqs, int64_t seq_byte
       int dev = 0;
       GB_HIP(hipGetDevice(&dev));
       Ws *W = nullptr;
-      if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+      if ((st = gb::get_ws(who, dev, &W, [](Ws *W) { return W->d_ctl.reserve(4); }))) return st;
       W->fill_ms = W->trace_ms = 0.f;
       W->cells = W->chunks = W->waves = W->ws_bytes = 0;
       if ((st = W->d_model.reserve(GB_ABEA_MODEL_SIZE)) || (st = W->d_seqs.reserve((size_t)seq_bytes)) ||

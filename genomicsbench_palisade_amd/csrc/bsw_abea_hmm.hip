@@ -259,10 +259,7 @@ static_assert(sizeof(DItem) == 56, "DItem is packed");
 static_assert(sizeof(gb_abea_hmm_read) == 40 && sizeof(gb_abea_hmm_item) == 32, "the header's records");
 static_assert(kTbl % 4 == 0 && kTbl * sizeof(float) <= 64 * 1024, "the table is staged as float4 into 64 KB");
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = 0, num_cus = 0;
-  gb::Stream stream;
-  gb::Event ev[2];
+struct Ws : gb::WsBase<2> {  // the calling thread's, through gb::get_ws
   gb::DevBuf<Model> d_model;
   gb::DevBuf<char> d_seqs;
   gb::DevBuf<float> d_events, d_flank, d_logsum, d_scores;
@@ -274,32 +271,17 @@ struct Ws {  // the calling thread's, through gb::thread_ws
   int64_t cells = 0, calls = 0;
 };
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
+static int make_tables(Ws *W) {  // the workspace's own part of gb::get_ws: the control words and the two tables
   const Tables &tb = tables();
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  int st = GB_ERR_HIP;
-  if (e != hipSuccess)
-    gb::set_error("gb_abea_hmm_score workspace: %s", hipGetErrorString(e));
-  else if (!(st = W->d_ctl.reserve(kClasses)) && !(st = W->d_flank.reserve((size_t)kMaxRows)) &&
-           !(st = W->d_logsum.reserve((size_t)kTbl))) {
-    e = hipMemcpy(W->d_flank, tb.flank.data(), (size_t)kMaxRows * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(W->d_logsum, tb.logsum, (size_t)kTbl * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      gb::set_error("gb_abea_hmm_score tables: %s", hipGetErrorString(e));
-      st = GB_ERR_HIP;
-    }
-  }
-  if (st) {
-    delete W;
+  int st;
+  if ((st = W->d_ctl.reserve(kClasses)) || (st = W->d_flank.reserve((size_t)kMaxRows)) ||
+      (st = W->d_logsum.reserve((size_t)kTbl)))
     return st;
-  }
-  *out = W;
-  return GB_OK;
+  hipError_t e = hipMemcpy(W->d_flank, tb.flank.data(), (size_t)kMaxRows * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(W->d_logsum, tb.logsum, (size_t)kTbl * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) return GB_OK;
+  gb::set_error("gb_abea_hmm_score tables: %s", hipGetErrorString(e));
+  return GB_ERR_HIP;
 }
 
 static int run_device(Ws *W, const gb_abea_hmm_read *reads, const gb_abea_hmm_item *items, int64_t n_items,
@@ -380,13 +362,8 @@ int gb_abea_hmm_logsum_table(float *out) {
 
 int gb_abea_hmm_timing(float *kernel_ms, int64_t *cells) {
   GB_ARG(kernel_ms && cells, "gb_abea_hmm_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbhmm::Ws *W = gb::find_thread_ws<gbhmm::Ws>(dev);
-  if (!W || !W->calls) {
-    gb::set_error("gb_abea_hmm_timing: gb_abea_hmm_score has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbhmm::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_abea_hmm_timing", "gb_abea_hmm_score", &W, &gbhmm::Ws::calls)) return st;
   *kernel_ms = W->kernel_ms, *cells = W->cells;
   return GB_OK;
 }
@@ -402,8 +379,7 @@ int gb_abea_hmm_score(const gb_abea_model *cpg_model, const char *seqs, int64_t 
     int st = validate(who, cpg_model, GB_ABEA_HMM_MODEL_SIZE, 1, 3, seqs, seq_bytes, event_mean, n_event_total, reads, n_reads,
                       items, n_items, scores, &trans);
     if (st || n_items == 0) return st;
-    const char *he = getenv("GB_ABEA_HOST");
-    if (he && *he == '1') {
+    if (gb::env_flag("GB_ABEA_HOST")) {
       int nth = 1;
       if ((st = gb::thread_count(who, "GB_ABEA_THREADS", &nth))) return st;
       const Tables &tb = tables();
@@ -426,7 +402,7 @@ int gb_abea_hmm_score(const gb_abea_model *cpg_model, const char *seqs, int64_t 
     int dev = 0;
     GB_HIP(hipGetDevice(&dev));
     Ws *W = nullptr;
-    if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+    if ((st = gb::get_ws(who, dev, &W, make_tables))) return st;
     W->calls = 0;
     if ((st = W->d_model.reserve(GB_ABEA_HMM_MODEL_SIZE)) || (st = W->d_seqs.reserve((size_t)seq_bytes)) ||
         (st = W->d_events.reserve((size_t)n_event_total)))

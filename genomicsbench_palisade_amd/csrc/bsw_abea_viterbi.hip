@@ -344,10 +344,7 @@ static_assert(sizeof(Model) == 12, "gb_abea_model is three floats");
 static_assert(sizeof(DItem) == 80, "DItem is packed");
 static_assert(sizeof(gb_abea_path_rec) == 16, "the header's record");
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = 0, num_cus = 0;
-  gb::Stream stream;
-  gb::Event ev[5];
+struct Ws : gb::WsBase<5> {  // the calling thread's, through gb::get_ws
   gb::DevBuf<Model> d_model;
   gb::DevBuf<char> d_seqs;
   gb::DevBuf<float> d_events;
@@ -365,66 +362,29 @@ struct Ws {  // the calling thread's, through gb::thread_ws
   int64_t cells = 0, calls = 0, chunks = 0, ws_bytes = 0;
 };
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  int st = GB_ERR_HIP;
-  if (e != hipSuccess)
-    gb::set_error("gb_abea_hmm_align workspace: %s", hipGetErrorString(e));
-  else
-    st = W->d_ctl.reserve(kClasses);
-  if (st) {
-    delete W;
-    return st;
-  }
-  *out = W;
-  return GB_OK;
-}
-
-struct Chunk {  // items [first, last) of the call
-  int64_t first, last, codes, records;
+struct Need {
+  int64_t codes, records;
   int64_t bytes() const {  // the codes, and the records walked and packed
     return codes * (int64_t)sizeof(uint16_t) + 2 * records * (int64_t)sizeof(gb_abea_path_rec);
   }
+  void operator+=(const Need &o) { codes += o.codes, records += o.records; }
+  void max_with(const Need &o) { codes = std::max(codes, o.codes), records = std::max(records, o.records); }
 };
+using Chunk = gb::Chunk<Need>;  // of the call's items
 
-static inline Chunk item_need(const gb_abea_hmm_item &it, int64_t i) {
+static inline Need item_need(const gb_abea_hmm_item &it) {
   const int nk = it.seq_len - kK + 1;
-  return Chunk{i, i + 1, item_codes(size_class(nk), nk, item_rows(it)), item_bound(it)};
+  return Need{item_codes(size_class(nk), nk, item_rows(it)), item_bound(it)};
 }
 
-// GB_ABEA_VITERBI_WS, or the default
-static int budget_bytes(const char *who, int64_t *out) {
-  *out = kDefaultBudget;
-  const char *e = getenv("GB_ABEA_VITERBI_WS");
-  if (!e || !*e) return GB_OK;
-  char *end = nullptr;
-  const long long v = strtoll(e, &end, 10);
-  GB_ARG(end && !*end && v > 0, "%s: GB_ABEA_VITERBI_WS is '%s' (need a number of bytes > 0)", who, e);
-  *out = v;
-  return GB_OK;
-}
-
-// The chunks of a call: items in order, as many as fit the budget. Refuses the item that alone does not.
-static int make_chunks(const char *who, const gb_abea_hmm_item *items, int64_t n_items, int64_t budget,
-                       std::vector<Chunk> *chunks) {
-  Chunk cur{0, 0, 0, 0};
-  for (int64_t i = 0; i < n_items; ++i) {
-    const Chunk one = item_need(items[i], i);
-    GB_ARG(one.bytes() <= budget,
-           "%s: item %lld needs %lld bytes of workspace, more than the budget of %lld (GB_ABEA_VITERBI_WS)", who,
-           (long long)i, (long long)one.bytes(), (long long)budget);
-    if (cur.last > cur.first && cur.bytes() + one.bytes() > budget) {
-      chunks->push_back(cur);
-      cur = Chunk{i, i, 0, 0};
-    }
-    cur.last = i + 1, cur.codes += one.codes, cur.records += one.records;
-  }
-  if (cur.last > cur.first) chunks->push_back(cur);
+// The chunks of a call: items in order, as many as fit GB_ABEA_VITERBI_WS or the default. Refuses the item that
+// alone does not.
+static int make_chunks(const char *who, const gb_abea_hmm_item *items, int64_t n_items, std::vector<Chunk> *chunks) {
+  int64_t budget = 0;
+  if (const int st = gb::env_number(who, "GB_ABEA_VITERBI_WS", 1, INT64_MAX, kDefaultBudget, &budget)) return st;
+  const int64_t i = gb::cut_chunks(n_items, budget, [&](int64_t k) { return item_need(items[k]); }, chunks);
+  GB_ARG(i < 0, "%s: item %lld needs %lld bytes of workspace, more than the budget of %lld (GB_ABEA_VITERBI_WS)", who,
+         (long long)i, (long long)item_need(items[i]).bytes(), (long long)budget);
   return GB_OK;
 }
 
@@ -544,26 +504,16 @@ extern "C" {
 
 int gb_abea_hmm_align_timing(float *fill_ms, float *walk_ms, int64_t *cells) {
   GB_ARG(fill_ms && walk_ms && cells, "gb_abea_hmm_align_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbvit::Ws *W = gb::find_thread_ws<gbvit::Ws>(dev);
-  if (!W || !W->calls) {
-    gb::set_error("gb_abea_hmm_align_timing: gb_abea_hmm_align has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbvit::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_abea_hmm_align_timing", "gb_abea_hmm_align", &W, &gbvit::Ws::calls)) return st;
   *fill_ms = W->fill_ms, *walk_ms = W->walk_ms, *cells = W->cells;
   return GB_OK;
 }
 
 int gb_abea_hmm_align_plan(int64_t *chunks, int64_t *workspace_bytes) {
   GB_ARG(chunks && workspace_bytes, "gb_abea_hmm_align_plan: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbvit::Ws *W = gb::find_thread_ws<gbvit::Ws>(dev);
-  if (!W || !W->calls) {
-    gb::set_error("gb_abea_hmm_align_plan: gb_abea_hmm_align has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbvit::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_abea_hmm_align_plan", "gb_abea_hmm_align", &W, &gbvit::Ws::calls)) return st;
   *chunks = W->chunks, *workspace_bytes = W->ws_bytes;
   return GB_OK;
 }
@@ -593,11 +543,9 @@ int gb_abea_hmm_align(const gb_abea_model *model, const char *seqs, int64_t seq_
              who, (long long)i);
       need += item_bound(it);
     }
-    const char *he = getenv("GB_ABEA_HOST");
-    const bool host = he && *he == '1';
+    const bool host = gb::env_flag("GB_ABEA_HOST");
     std::vector<Chunk> chunks;
-    int64_t budget = 0;
-    if (!host && ((st = budget_bytes(who, &budget)) || (st = make_chunks(who, items, n_items, budget, &chunks)))) return st;
+    if (!host && (st = make_chunks(who, items, n_items, &chunks))) return st;
     if (path_cap < need) {
       *path_used = need;
       gb::set_error("%s: path_cap is %lld, the items need %lld (rows + k-mers - 1 each)", who, (long long)path_cap,
@@ -637,19 +585,15 @@ int gb_abea_hmm_align(const gb_abea_model *model, const char *seqs, int64_t seq_
     if ((st = gb::thread_count(who, "GB_ABEA_THREADS", &nth))) return st;  // for the copy into path
     GB_HIP(hipGetDevice(&dev));
     Ws *W = nullptr;
-    if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+    if ((st = gb::get_ws(who, dev, &W, [](Ws *W) { return W->d_ctl.reserve(kClasses); }))) return st;
     W->calls = 0, W->cells = 0, W->fill_ms = W->walk_ms = 0.f;
-    Chunk big{0, 0, 0, 0};  // every buffer at the largest any chunk asks of it, so that none grows between chunks
-    int64_t big_n = 0, big_bytes = 0;
-    for (const Chunk &c : chunks) {
-      big.codes = std::max(big.codes, c.codes), big.records = std::max(big.records, c.records);
-      big_n = std::max(big_n, c.last - c.first), big_bytes = std::max(big_bytes, c.bytes());
-    }
+    const auto big = gb::largest(chunks);  // every buffer at the largest any chunk asks of it
+    const int64_t big_n = big.count;
     if ((st = W->d_model.reserve(GB_ABEA_VITERBI_MODEL_SIZE)) || (st = W->d_seqs.reserve((size_t)seq_bytes)) ||
         (st = W->d_events.reserve((size_t)n_event_total)) || (st = W->h_items.reserve((size_t)big_n + 3)) ||
-        (st = W->d_items.reserve((size_t)big_n + 3)) || (st = W->d_codes.reserve((size_t)big.codes)) ||
-        (st = W->d_path.reserve((size_t)big.records)) || (st = W->d_packed.reserve((size_t)big.records)) ||
-        (st = W->h_path.reserve((size_t)big.records)) || (st = W->d_lens.reserve((size_t)big_n)) ||
+        (st = W->d_items.reserve((size_t)big_n + 3)) || (st = W->d_codes.reserve((size_t)big.need.codes)) ||
+        (st = W->d_path.reserve((size_t)big.need.records)) || (st = W->d_packed.reserve((size_t)big.need.records)) ||
+        (st = W->h_path.reserve((size_t)big.need.records)) || (st = W->d_lens.reserve((size_t)big_n)) ||
         (st = W->h_lens.reserve((size_t)big_n)) || (st = W->d_offs.reserve((size_t)big_n)) ||
         (st = W->h_offs.reserve((size_t)big_n)))
       return st;
@@ -661,7 +605,7 @@ int gb_abea_hmm_align(const gb_abea_model *model, const char *seqs, int64_t seq_
     for (const Chunk &c : chunks)
       if ((st = run_chunk(W, nth, c, reads, items, trans, path, path_off, &used))) return st;
     path_off[n_items] = *path_used = used;
-    W->chunks = (int64_t)chunks.size(), W->ws_bytes = big_bytes;
+    W->chunks = (int64_t)chunks.size(), W->ws_bytes = big.bytes;
     W->calls = 1;
     return GB_OK;
   } catch (const std::bad_alloc &) {

@@ -802,13 +802,8 @@ int gb_bsw_gen_cigar_retry(const gb_bsw_params *params, const gb_ref *ref, gb_bs
 
 int gb_bsw_gen_cigar_timing(float *fetch_ms, float *fill_ms, float *walk_ms, float *md_ms) {
   GB_ARG(fetch_ms && fill_ms && walk_ms && md_ms, "gb_bsw_gen_cigar_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbgc::GWs *G = gb::find_thread_ws<gbgc::GWs>(dev);
-  if (!G) {
-    gb::set_error("gb_bsw_gen_cigar_timing: gb_bsw_gen_cigar has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbgc::GWs *G = nullptr;
+  if (const int st = gb::ran_ws("gb_bsw_gen_cigar_timing", "gb_bsw_gen_cigar", &G)) return st;
   *fetch_ms = G->fetch_ms;
   *fill_ms = G->fill_ms;
   *walk_ms = G->walk_ms;

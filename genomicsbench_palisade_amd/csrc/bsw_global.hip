@@ -298,27 +298,9 @@ int64_t dir_words_limit() {  // GB_BSW_GLOBAL_DIR_WORDS (tests: many chunks from
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kDirWords)) : kDirWords;
 }
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  int st = GB_ERR_HIP;
-  if (e == hipSuccess)
-    st = W->d_ctl.reserve(4);
-  else
-    gb::set_error("gb_bsw_global workspace: %s", hipGetErrorString(e));
-  if (st) {
-    delete W;
-    return st;
-  }
-  *out = W;
-  return GB_OK;
+int get_ws(int dev, Ws **out) {
+  return gb::get_ws("gb_bsw_global", dev, out, [](Ws *W) { return W->d_ctl.reserve(4); });
 }
-
-int get_ws(int dev, Ws **out) { return gb::thread_ws(dev, out, make_ws); }
 
 // Every refusal of include/gb_bsw.h, before any device work.
 int validate(const gb_bsw_params *params, const gb_bsw_gpair *pairs, int64_t n, const uint8_t *ref, int64_t ref_bytes,
@@ -364,13 +346,8 @@ int gb_bsw_global_band(const gb_bsw_params *params, int32_t len2, int32_t len1, 
 
 int gb_bsw_global_timing(float *fill_ms, float *walk_ms) {
   GB_ARG(fill_ms && walk_ms, "gb_bsw_global_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbbswg::Ws *W = gb::find_thread_ws<gbbswg::Ws>(dev);
-  if (!W) {
-    gb::set_error("gb_bsw_global_timing: gb_bsw_global has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbbswg::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_bsw_global_timing", "gb_bsw_global", &W)) return st;
   *fill_ms = W->fill_ms;
   *walk_ms = W->walk_ms;
   return GB_OK;

@@ -23,10 +23,7 @@ __host__ __device__ inline int row_words(int qlen) {  // lanes owning a query co
   return (qlen + K - 1) / K;
 }
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = -1, num_cus = 256;
-  gb::Stream stream;
-  gb::Event ev[3];
+struct Ws : gb::WsBase<3> {  // the calling thread's, through get_ws
   gb::DevBuf<uint8_t> d_tgt, d_qry;
   gb::DevBuf<Pair> d_pairs;
   gb::DevBuf<int32_t> d_out4;

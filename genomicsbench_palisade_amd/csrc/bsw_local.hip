@@ -287,27 +287,9 @@ int64_t chunk_pairs() {  // GB_BSW_LOCAL_CHUNK (tests: many chunks from a small 
   return e ? std::max<int64_t>(1, std::min<int64_t>(atoll(e), kChunkPairs)) : kChunkPairs;
 }
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  int st = GB_ERR_HIP;
-  if (e == hipSuccess)
-    st = W->d_ctl.reserve(4);
-  else
-    gb::set_error("gb_bsw_local workspace: %s", hipGetErrorString(e));
-  if (st) {
-    delete W;
-    return st;
-  }
-  *out = W;
-  return GB_OK;
+int get_ws(int dev, Ws **out) {
+  return gb::get_ws("gb_bsw_local", dev, out, [](Ws *W) { return W->d_ctl.reserve(4); });
 }
-
-int get_ws(int dev, Ws **out) { return gb::thread_ws(dev, out, make_ws); }
 
 int run_resident(Ws *W, const gb_bsw_params *params, int max_mat, const Pair *d_pairs, int64_t m, const uint8_t *d_tgt,
                  const uint8_t *d_qry, int32_t *d_out8, int64_t list_cap, hipEvent_t e0, hipEvent_t e1) {
@@ -391,13 +373,8 @@ int gb_bsw_local_xtra(const gb_bsw_params *params, int32_t len2, int32_t min_see
 
 int gb_bsw_local_timing(float *kernel_ms) {
   GB_ARG(kernel_ms, "gb_bsw_local_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbbswl::Ws *W = gb::find_thread_ws<gbbswl::Ws>(dev);
-  if (!W) {
-    gb::set_error("gb_bsw_local_timing: gb_bsw_local has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbbswl::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_bsw_local_timing", "gb_bsw_local", &W)) return st;
   *kernel_ms = W->kernel_ms;
   return GB_OK;
 }

@@ -19,10 +19,7 @@ struct Pair {  // device descriptor, 32 B
 // entries a pass over tlen rows can append: never on two adjacent rows (ksw.c:193)
 __host__ __device__ inline int64_t list_entries(int tlen) { return (tlen + 1) / 2 + 1; }
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = -1, num_cus = 256;
-  gb::Stream stream;
-  gb::Event ev[2];
+struct Ws : gb::WsBase<2> {  // the calling thread's, through get_ws
   gb::DevBuf<uint8_t> d_tgt, d_qry;
   gb::DevBuf<Pair> d_pairs;
   gb::DevBuf<int32_t> d_out8;

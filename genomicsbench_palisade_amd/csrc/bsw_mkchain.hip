@@ -927,8 +927,7 @@ static int seeds2chains_impl(const gb_bsw_chain_opt *opt, int32_t stage, int64_t
                              int64_t *seeds_used) {
   using namespace gbmk;
   const char *who = "gb_bsw_seeds2chains";
-  const char *he = getenv("GB_BSW_MKCHAIN_HOST");
-  const bool all_host = he && *he == '1';
+  const bool all_host = gb::env_flag("GB_BSW_MKCHAIN_HOST");
   // GB_BSW_MKCHAIN_DEV_COORDS lowers (or raises) the bound above which a read takes the host path: the
   // tests reach the mixed call with it
   int64_t dev_coords = GB_BSW_MKCHAIN_DEV_COORDS;

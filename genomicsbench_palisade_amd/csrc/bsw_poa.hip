@@ -469,9 +469,7 @@ static Stats &stats() {
   return s;
 }
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  gb::Stream stream;
-  gb::Event ev[3];
+struct Ws : gb::WsBase<3> {  // the calling thread's, through gb::get_ws
   gb::DevBuf<uint8_t> d_base, d_out, d_seqs;
   gb::DevBuf<int32_t> d_id, d_in_end, d_pred, d_mats, d_walked;
   gb::DevBuf<DItem> d_items;
@@ -480,35 +478,6 @@ struct Ws {  // the calling thread's, through gb::thread_ws
   gb::PinnedBuf<DRes> h_res;
   gb::PinnedBuf<int32_t> h_walked;
 };
-
-static int make_ws(int, Ws **out) {
-  auto *W = new Ws();
-  hipError_t e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  if (e != hipSuccess) {
-    gb::set_error("gb_poa workspace: %s", hipGetErrorString(e));
-    delete W;
-    return GB_ERR_HIP;
-  }
-  *out = W;
-  return GB_OK;
-}
-
-static int budget_bytes(const char *who, int64_t *out) {
-  *out = kDefaultBudget;
-  const char *e = getenv("GB_POA_WS");
-  if (!e || !*e) return GB_OK;
-  char *end = nullptr;
-  const long long v = strtoll(e, &end, 10);
-  GB_ARG(end && !*end && v > 0, "%s: GB_POA_WS is '%s' (need a number of bytes > 0)", who, e);
-  *out = v;
-  return GB_OK;
-}
-static bool host_path() {
-  const char *he = getenv("GB_POA_HOST");
-  return he && *he == '1';
-}
 
 static inline bool live_item(const gb_poa_item &it) { return it.n_nodes > 0 && it.seq_len > 0; }
 
@@ -547,27 +516,24 @@ static int validate(const char *who, const char *what, const Batch &B) {
   return GB_OK;
 }
 
-struct Chunk {
-  int64_t first, last, words /* of matrices */, pairs;
+struct Need {
+  int64_t words /* of matrices */, pairs;
   int64_t bytes() const { return words * 4 + pairs * 8; }
+  void operator+=(const Need &o) { words += o.words, pairs += o.pairs; }
+  void max_with(const Need &o) { words = std::max(words, o.words), pairs = std::max(pairs, o.pairs); }
 };
+using Chunk = gb::Chunk<Need>;  // of the live items
 
+// The chunks of a batch: the live items in order, as many as fit the budget. Refuses the item that alone does not.
 static int make_chunks(const char *who, const char *what, const int64_t *names, const Par &P, const Batch &B,
                        const std::vector<int64_t> &live, int64_t budget, std::vector<Chunk> *chunks) {
-  Chunk cur{0, 0, 0, 0};
-  for (int64_t k = 0; k < (int64_t)live.size(); ++k) {
+  auto need_of = [&](int64_t k) {
     const gb_poa_item &it = B.items[live[(size_t)k]];
-    const Chunk one{k, k + 1, mat_words(P.sub, it.n_nodes, it.seq_len), (int64_t)it.n_nodes + it.seq_len};
-    const int64_t name = names ? names[live[(size_t)k]] : live[(size_t)k];
-    GB_ARG(one.bytes() <= budget, "%s: %s %lld needs %lld bytes of workspace, more than the budget of %lld (GB_POA_WS)",
-           who, what, (long long)name, (long long)one.bytes(), (long long)budget);
-    if (cur.last > cur.first && cur.bytes() + one.bytes() > budget) {
-      chunks->push_back(cur);
-      cur = Chunk{k, k, 0, 0};
-    }
-    cur.last = k + 1, cur.words += one.words, cur.pairs += one.pairs;
-  }
-  if (cur.last > cur.first) chunks->push_back(cur);
+    return Need{mat_words(P.sub, it.n_nodes, it.seq_len), (int64_t)it.n_nodes + it.seq_len};
+  };
+  const int64_t k = gb::cut_chunks((int64_t)live.size(), budget, need_of, chunks);
+  GB_ARG(k < 0, "%s: %s %lld needs %lld bytes of workspace, more than the budget of %lld (GB_POA_WS)", who, what,
+         (long long)(names ? names[live[(size_t)k]] : live[(size_t)k]), (long long)need_of(k).bytes(), (long long)budget);
   return GB_OK;
 }
 
@@ -628,12 +594,9 @@ static int run_batch(const char *who, const char *what, const int64_t *names, co
   int dev = 0;
   GB_HIP(hipGetDevice(&dev));
   Ws *W = nullptr;
-  if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
-  int64_t big_words = 0, big_pairs = 0, big_n = 0, big_bytes = 0;
-  for (const Chunk &c : chunks) {
-    big_words = std::max(big_words, c.words), big_pairs = std::max(big_pairs, c.pairs);
-    big_n = std::max(big_n, c.last - c.first), big_bytes = std::max(big_bytes, c.bytes());
-  }
+  if ((st = gb::get_ws("gb_poa", dev, &W))) return st;
+  const auto big = gb::largest(chunks);
+  const int64_t big_words = big.need.words, big_pairs = big.need.pairs, big_n = big.count;
   const gb_poa_graphs &g = B.g;
   if ((st = W->d_base.reserve((size_t)g.n_nodes)) || (st = W->d_out.reserve((size_t)g.n_nodes)) ||
       (st = W->d_id.reserve((size_t)g.n_nodes)) || (st = W->d_in_end.reserve((size_t)g.n_nodes)) ||
@@ -687,7 +650,7 @@ static int run_batch(const char *who, const char *what, const int64_t *names, co
     GB_HIP(hipGetLastError());
     GB_HIP(hipEventRecord(W->ev[2], s));
     GB_HIP(hipMemcpyAsync(W->h_res, W->d_res, (size_t)n * sizeof(DRes), hipMemcpyDeviceToHost, s));
-    GB_HIP(hipMemcpyAsync(W->h_walked, W->d_walked, (size_t)ch.pairs * 8, hipMemcpyDeviceToHost, s));
+    GB_HIP(hipMemcpyAsync(W->h_walked, W->d_walked, (size_t)ch.need.pairs * 8, hipMemcpyDeviceToHost, s));
     GB_HIP(hipStreamSynchronize(s));
     float fill_ms = 0.f, walk_ms = 0.f;
     GB_HIP(hipEventElapsedTime(&fill_ms, W->ev[0], W->ev[1]));
@@ -705,7 +668,7 @@ static int run_batch(const char *who, const char *what, const int64_t *names, co
       po += cap;
     }
   }
-  S.chunks += (int64_t)chunks.size(), S.ws_bytes = std::max(S.ws_bytes, big_bytes);
+  S.chunks += (int64_t)chunks.size(), S.ws_bytes = std::max(S.ws_bytes, big.bytes);
   return GB_OK;
 }
 
@@ -971,10 +934,11 @@ int gb_poa_align(const gb_poa_params *p, const gb_poa_graphs *g, const uint8_t *
       begin[(size_t)i] = need;
       if (live_item(items[i])) live.push_back(i), need += (int64_t)items[i].n_nodes + items[i].seq_len;
     }
-    const bool host = host_path();
+    const bool host = gb::env_flag("GB_POA_HOST");
     std::vector<Chunk> chunks;
     int64_t budget = 0;
-    if (!host && ((st = budget_bytes(who, &budget)) || (st = make_chunks(who, "item", nullptr, P, B, live, budget, &chunks))))
+    if (!host && ((st = gb::env_number(who, "GB_POA_WS", 1, INT64_MAX, kDefaultBudget, &budget)) ||
+                  (st = make_chunks(who, "item", nullptr, P, B, live, budget, &chunks))))
       return st;
     if (pair_cap < need) {
       *pair_used = need;
@@ -1037,9 +1001,9 @@ int gb_poa_consensus(const gb_poa_params *p, const int64_t *win_off, int64_t n_w
              (long long)(seq_off[win_off[w + 1]] - seq_off[win_off[w]]), GB_POA_MAX_NODES);
       max_round = std::max(max_round, win_off[w + 1] - win_off[w]);
     }
-    const bool host = host_path();
+    const bool host = gb::env_flag("GB_POA_HOST");
     int64_t budget = 0;
-    if (!host && (st = budget_bytes(who, &budget))) return st;
+    if (!host && (st = gb::env_number(who, "GB_POA_WS", 1, INT64_MAX, kDefaultBudget, &budget))) return st;
     const int64_t need = n_seqs ? seq_off[n_seqs] - seq_off[0] : 0;
     if (cons_cap < need) {
       *cons_used = need;

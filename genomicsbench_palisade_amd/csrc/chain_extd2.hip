@@ -347,10 +347,9 @@ __global__ __launch_bounds__(256) void extd2_pack_kernel(Args A) {
   }
 }
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  int device = 0, num_cus = 0;
-  gb::Stream stream, side[kStreams - 1];  // the fill's launches are spread over `stream` and these
-  gb::Event ev[5], fork, join[kStreams - 1];
+struct Ws : gb::WsBase<5> {  // the calling thread's, through gb::get_ws
+  gb::Stream side[kStreams - 1];  // the fill's launches are spread over `stream` and these
+  gb::Event fork, join[kStreams - 1];
   gb::DevBuf<uint8_t> d_seqs, d_codes, d_state;
   gb::DevBuf<DItem> d_items;
   gb::DevBuf<gb_chain_extd2_result> d_res;
@@ -364,65 +363,40 @@ struct Ws {  // the calling thread's, through gb::thread_ws
   int64_t cells = 0, calls = 0, chunks = 0, ws_bytes = 0;
 };
 
-static int make_ws(int dev, Ws **out) {
-  auto *W = new Ws();
-  W->device = dev;
-  hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
+static hipError_t make_sides(Ws *W) {  // the workspace's own part of gb::get_ws, which words the error
+  hipError_t e = hipSuccess;
   for (auto &st : W->side)
     if (e == hipSuccess) e = st.create();
   for (auto &ev : W->join)
     if (e == hipSuccess) e = ev.create();
-  if (e == hipSuccess) e = W->fork.create();
-  if (e != hipSuccess) {
-    gb::set_error("gb_chain_extd2 workspace: %s", hipGetErrorString(e));
-    delete W;
-    return GB_ERR_HIP;
-  }
-  *out = W;
-  return GB_OK;
+  return e == hipSuccess ? W->fork.create() : e;
 }
 
-struct Chunk {  // the live items [first, last) of the call's list of them
-  int64_t first, last, codes, state, words;
+struct Need {
+  int64_t codes, state, words;
   int64_t bytes() const { return codes + state + 2 * words * (int64_t)sizeof(uint32_t); }
-};
-
-static inline Chunk item_need(const gb_chain_extd2_item &it, int64_t k) {
-  const int64_t st = size_class(it) == 3 ? gb::round_up(state_bytes(it.qlen, it.tlen), 16) : 0;
-  return Chunk{k, k + 1, item_codes(it), st, (int64_t)it.qlen + it.tlen};
-}
-
-// GB_CHAIN_EXTD2_WS, or the default
-static int budget_bytes(const char *who, int64_t *out) {
-  *out = kDefaultBudget;
-  const char *e = getenv("GB_CHAIN_EXTD2_WS");
-  if (!e || !*e) return GB_OK;
-  char *end = nullptr;
-  const long long v = strtoll(e, &end, 10);
-  GB_ARG(end && !*end && v > 0, "%s: GB_CHAIN_EXTD2_WS is '%s' (need a number of bytes > 0)", who, e);
-  *out = v;
-  return GB_OK;
-}
-
-// The chunks of a call: the live items in order, as many as fit the budget. Refuses the item that alone does not.
-static int make_chunks(const char *who, const gb_chain_extd2_item *items, const std::vector<int64_t> &live,
-                       int64_t budget, std::vector<Chunk> *chunks) {
-  Chunk cur{0, 0, 0, 0, 0};
-  for (int64_t k = 0; k < (int64_t)live.size(); ++k) {
-    const Chunk one = item_need(items[live[(size_t)k]], k);
-    GB_ARG(one.bytes() <= budget,
-           "%s: item %lld needs %lld bytes of workspace, more than the budget of %lld (GB_CHAIN_EXTD2_WS)", who,
-           (long long)live[(size_t)k], (long long)one.bytes(), (long long)budget);
-    if (cur.last > cur.first && cur.bytes() + one.bytes() > budget) {
-      chunks->push_back(cur);
-      cur = Chunk{k, k, 0, 0, 0};
-    }
-    cur.last = k + 1, cur.codes += one.codes, cur.state += one.state, cur.words += one.words;
+  void operator+=(const Need &o) { codes += o.codes, state += o.state, words += o.words; }
+  void max_with(const Need &o) {
+    codes = std::max(codes, o.codes), state = std::max(state, o.state), words = std::max(words, o.words);
   }
-  if (cur.last > cur.first) chunks->push_back(cur);
+};
+using Chunk = gb::Chunk<Need>;  // of the call's list of live items
+
+static inline Need item_need(const gb_chain_extd2_item &it) {
+  const int64_t st = size_class(it) == 3 ? gb::round_up(state_bytes(it.qlen, it.tlen), 16) : 0;
+  return Need{item_codes(it), st, (int64_t)it.qlen + it.tlen};
+}
+
+// The chunks of a call: the live items in order, as many as fit GB_CHAIN_EXTD2_WS or the default. Refuses the item
+// that alone does not.
+static int make_chunks(const char *who, const gb_chain_extd2_item *items, const std::vector<int64_t> &live,
+                       std::vector<Chunk> *chunks) {
+  int64_t budget = 0;
+  if (const int st = gb::env_number(who, "GB_CHAIN_EXTD2_WS", 1, INT64_MAX, kDefaultBudget, &budget)) return st;
+  auto need_of = [&](int64_t k) { return item_need(items[live[(size_t)k]]); };
+  const int64_t k = gb::cut_chunks((int64_t)live.size(), budget, need_of, chunks);
+  GB_ARG(k < 0, "%s: item %lld needs %lld bytes of workspace, more than the budget of %lld (GB_CHAIN_EXTD2_WS)", who,
+         (long long)live[(size_t)k], (long long)need_of(k).bytes(), (long long)budget);
   return GB_OK;
 }
 
@@ -451,7 +425,7 @@ static int run_chunk(Ws *W, const Par &P, const Chunk &ch, const gb_chain_extd2_
   std::vector<int64_t> code_off((size_t)n), state_off((size_t)n), cig_off((size_t)n);
   int64_t co = 0, so = 0, wo = 0;
   for (int64_t i = 0; i < n; ++i) {  // the buffers in item order
-    const Chunk one = item_need(items[live[(size_t)(ch.first + i)]], i);
+    const Need one = item_need(items[live[(size_t)(ch.first + i)]]);
     code_off[(size_t)i] = co, state_off[(size_t)i] = so, cig_off[(size_t)i] = wo;
     co += one.codes, so += one.state, wo += one.words;
   }
@@ -537,26 +511,16 @@ extern "C" {
 
 int gb_chain_extd2_timing(float *fill_ms, float *walk_ms, int64_t *cells) {
   GB_ARG(fill_ms && walk_ms && cells, "gb_chain_extd2_timing: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbx2::Ws *W = gb::find_thread_ws<gbx2::Ws>(dev);
-  if (!W || !W->calls) {
-    gb::set_error("gb_chain_extd2_timing: gb_chain_extd2 has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbx2::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_chain_extd2_timing", "gb_chain_extd2", &W, &gbx2::Ws::calls)) return st;
   *fill_ms = W->fill_ms, *walk_ms = W->walk_ms, *cells = W->cells;
   return GB_OK;
 }
 
 int gb_chain_extd2_plan(int64_t *chunks, int64_t *workspace_bytes) {
   GB_ARG(chunks && workspace_bytes, "gb_chain_extd2_plan: null argument");
-  int dev = 0;
-  GB_HIP(hipGetDevice(&dev));
-  const gbx2::Ws *W = gb::find_thread_ws<gbx2::Ws>(dev);
-  if (!W || !W->calls) {
-    gb::set_error("gb_chain_extd2_plan: gb_chain_extd2 has not run on this thread and device");
-    return GB_ERR_STATE;
-  }
+  const gbx2::Ws *W = nullptr;
+  if (const int st = gb::ran_ws("gb_chain_extd2_plan", "gb_chain_extd2", &W, &gbx2::Ws::calls)) return st;
   *chunks = W->chunks, *workspace_bytes = W->ws_bytes;
   return GB_OK;
 }
@@ -600,12 +564,10 @@ int gb_chain_extd2(const gb_chain_extd2_params *p, const uint8_t *seqs, int64_t 
       cigar_off[0] = 0, *cigar_used = 0;
       return GB_OK;
     }
-    const char *he = getenv("GB_CHAIN_EXTD2_HOST");
-    const bool host = he && *he == '1';
+    const bool host = gb::env_flag("GB_CHAIN_EXTD2_HOST");
     std::vector<Chunk> chunks;
-    int64_t budget = 0;
     int st;
-    if (!host && ((st = budget_bytes(who, &budget)) || (st = make_chunks(who, items, live, budget, &chunks)))) return st;
+    if (!host && (st = make_chunks(who, items, live, &chunks))) return st;
     if (cigar_cap < need) {
       *cigar_used = need;
       gb::set_error("%s: cigar_cap is %lld, the items need %lld (qlen + tlen each)", who, (long long)cigar_cap,
@@ -641,29 +603,24 @@ int gb_chain_extd2(const gb_chain_extd2_params *p, const uint8_t *seqs, int64_t 
       int dev = 0;
       GB_HIP(hipGetDevice(&dev));
       Ws *W = nullptr;
-      if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+      if ((st = gb::get_ws(who, dev, &W, make_sides))) return st;
       W->calls = 0, W->cells = 0, W->fill_ms = W->walk_ms = 0.f;
-      Chunk big{0, 0, 0, 0, 0};  // every buffer at the largest any chunk asks of it
-      int64_t big_n = 0, big_bytes = 0;
-      for (const Chunk &c : chunks) {
-        big.codes = std::max(big.codes, c.codes), big.state = std::max(big.state, c.state);
-        big.words = std::max(big.words, c.words);
-        big_n = std::max(big_n, c.last - c.first), big_bytes = std::max(big_bytes, c.bytes());
-      }
-      if ((st = W->d_seqs.reserve((size_t)seq_bytes)) || (st = W->d_codes.reserve((size_t)big.codes)) ||
-          (st = W->d_state.reserve((size_t)big.state)) || (st = W->d_items.reserve((size_t)big_n)) ||
+      const auto big = gb::largest(chunks);  // every buffer at the largest any chunk asks of it
+      const int64_t big_n = big.count;
+      if ((st = W->d_seqs.reserve((size_t)seq_bytes)) || (st = W->d_codes.reserve((size_t)big.need.codes)) ||
+          (st = W->d_state.reserve((size_t)big.need.state)) || (st = W->d_items.reserve((size_t)big_n)) ||
           (st = W->h_items.reserve((size_t)big_n)) || (st = W->d_res.reserve((size_t)big_n)) ||
           (st = W->h_res.reserve((size_t)big_n)) || (st = W->d_cells.reserve((size_t)big_n)) ||
           (st = W->h_cells.reserve((size_t)big_n)) || (st = W->d_offs.reserve((size_t)big_n)) ||
-          (st = W->h_offs.reserve((size_t)big_n)) || (st = W->d_walked.reserve((size_t)big.words)) ||
-          (st = W->d_packed.reserve((size_t)big.words)) || (st = W->h_packed.reserve((size_t)big.words)))
+          (st = W->h_offs.reserve((size_t)big_n)) || (st = W->d_walked.reserve((size_t)big.need.words)) ||
+          (st = W->d_packed.reserve((size_t)big.need.words)) || (st = W->h_packed.reserve((size_t)big.need.words)))
         return st;
       GB_HIP(hipMemcpyAsync(W->d_seqs, seqs, (size_t)seq_bytes, hipMemcpyHostToDevice, W->stream));
       // an item that returns early keeps the offset of the next live one (it owns no words)
       for (int64_t i = 0; i < n_items; ++i) cigar_off[i] = -1;
       for (const Chunk &c : chunks)
         if ((st = run_chunk(W, P, c, items, live, res, cigar, cigar_off, &used))) return st;
-      W->chunks = (int64_t)chunks.size(), W->ws_bytes = big_bytes;
+      W->chunks = (int64_t)chunks.size(), W->ws_bytes = big.bytes;
       W->calls = 1;
     }
     cigar_off[n_items] = *cigar_used = used;

@@ -73,21 +73,6 @@ struct Round {
 
 // ------------------------------------------------------------------------------------------------------- device
 
-__device__ __forceinline__ int block_scan_excl(int v, int *total, int *lds) {
-  const int inc = gb::scan_add(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 63) lds[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int i = 0; i < kThreads / 64; ++i) {
-    const int t = lds[i];
-    if (i < (int)(threadIdx.x >> 6)) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 // the text that holds edge e: the t with eb[t] <= e < eb[t + 1] (texts without an edge are passed over)
 __device__ __forceinline__ int text_of(const int32_t *eb, int n_texts, int e) {
   int lo = 0, hi = n_texts - 1;
@@ -247,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void k_dbg_rank(const Reg *regs, Scratch 
       n += slot[j] != kNone;
     }
     int total;
-    int id = carry + block_scan_excl(n, &total, lds);
+    int id = carry + gb::block_scan_excl<kThreads>(n, &total, lds);
     for (int j = 0; j < kScanItems; ++j)
       if (slot[j] != kNone) {
         if (id < R.node_cap) nid[slot[j]] = (uint32_t)id, n_first[id] = (uint32_t)(base + j), n_slot[id] = slot[j];
@@ -409,39 +394,8 @@ Stats &stats() {
   return s;
 }
 
-struct Ws {
-  gb::Stream stream;
-  gb::Event ev[6];
-};
-int make_ws(int, Ws **out) {
-  auto *W = new Ws();
-  hipError_t e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  if (e != hipSuccess) {
-    gb::set_error("gb_dbg workspace: %s", hipGetErrorString(e));
-    delete W;
-    return GB_ERR_HIP;
-  }
-  *out = W;
-  return GB_OK;
-}
+struct Ws : gb::WsBase<6> {};  // the calling thread's, through gb::get_ws
 
-int env_number(const char *who, const char *name, int64_t lo, int64_t hi, int64_t dflt, int64_t *out) {
-  *out = dflt;
-  const char *e = getenv(name);
-  if (!e || !*e) return GB_OK;
-  char *end = nullptr;
-  const long long v = strtoll(e, &end, 10);
-  GB_ARG(end && !*end && v >= lo && v <= hi, "%s: %s is '%s' (need a number in %lld..%lld)", who, name, e,
-         (long long)lo, (long long)hi);
-  *out = v;
-  return GB_OK;
-}
-bool host_path() {
-  const char *he = getenv("GB_DBG_HOST");
-  return he && *he == '1';
-}
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -598,7 +552,7 @@ int assemble_device(const char *who, const Input &in, int64_t n_regions, int64_t
   int st, dev = -1;
   GB_HIP(hipGetDevice(&dev));
   Ws *W = nullptr;
-  if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+  if ((st = gb::get_ws("gb_dbg", dev, &W))) return st;
   hipStream_t s = W->stream;
   Stats &S = stats();
 
@@ -816,9 +770,9 @@ int gb_dbg_assemble(const uint8_t *ref_bytes, int64_t n_ref_bytes, const int64_t
   in.ref_start = ref_start, in.read_first = read_first, in.read_last = read_last, in.flag = flag;
   int64_t budget = 0, fp_bits = 64;
   int st;
-  if ((st = env_number(who, "GB_DBG_WS", 1, INT64_MAX, kDefaultBudget, &budget))) return st;
-  if ((st = env_number(who, "GB_DBG_FP_BITS", 1, 64, 64, &fp_bits))) return st;
-  const bool on_host = host_path();
+  if ((st = gb::env_number(who, "GB_DBG_WS", 1, INT64_MAX, kDefaultBudget, &budget))) return st;
+  if ((st = gb::env_number(who, "GB_DBG_FP_BITS", 1, 64, 64, &fp_bits))) return st;
+  const bool on_host = gb::env_flag("GB_DBG_HOST");
   std::vector<Plan> plan;
   gb_dbg *h = nullptr;
   try {

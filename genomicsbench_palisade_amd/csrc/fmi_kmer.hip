@@ -40,22 +40,6 @@ constexpr uint32_t kStrand = 0x80000000u, kRank = 0x7FFFFFFFu;
 
 // ---------------------------------------------------------------------------------------------- device: scans
 
-// exclusive scan of v over the 256 lanes of the workgroup and the workgroup's total; lds has 4 ints
-__device__ __forceinline__ int block_scan_excl(int v, int *total, int *lds) {
-  const int inc = gb::scan_add(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 63) lds[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int i = 0; i < kThreads / 64; ++i) {
-    const int t = lds[i];
-    if (i < (int)(threadIdx.x >> 6)) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kThreads) void k_scan_sums(const T *in, int64_t n, uint32_t *sums) {
   __shared__ int lds[4];
@@ -64,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_sums(const T *in, int64_t n, 
   for (int j = 0; j < kItems; ++j)
     if (base + j < n) s += (int)in[base + j];
   int total;
-  block_scan_excl(s, &total, lds);
+  gb::block_scan_excl<kThreads>(s, &total, lds);
   if (threadIdx.x == 0) sums[blockIdx.x] = (uint32_t)total;
 }
 
@@ -76,7 +60,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_top(uint32_t *sums, int64_t n
     const int64_t i = c + threadIdx.x;
     const int v = i < nb ? (int)sums[i] : 0;
     int total;
-    const int ex = block_scan_excl(v, &total, lds);
+    const int ex = gb::block_scan_excl<kThreads>(v, &total, lds);
     if (i < nb) sums[i] = (uint32_t)(carry + ex);
     carry += total;
   }
@@ -94,7 +78,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_apply(const T *in, int64_t n,
     s += v[j];
   }
   int total;
-  int ex = block_scan_excl(s, &total, lds) + (int)sums[blockIdx.x];
+  int ex = gb::block_scan_excl<kThreads>(s, &total, lds) + (int)sums[blockIdx.x];
   for (int j = 0; j < kItems; ++j) {
     if (base + j < n) out[base + j] = (uint32_t)ex;
     ex += v[j];
@@ -228,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void k_stats(const uint32_t *counts, int6
     mx = max(mx, c), over += c >= 16;
   }
   int total;
-  block_scan_excl(over, &total, lds);
+  gb::block_scan_excl<kThreads>(over, &total, lds);
   mx = gb::wave_max<0>(mx);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mx;
@@ -370,38 +354,7 @@ Stats &stats() {
   return s;
 }
 
-struct Ws {  // the calling thread's, through gb::thread_ws
-  gb::Stream stream;
-  gb::Event ev[5];
-};
-int make_ws(int, Ws **out) {
-  auto *W = new Ws();
-  hipError_t e = W->stream.create();
-  for (auto &ev : W->ev)
-    if (e == hipSuccess) e = ev.create();
-  if (e != hipSuccess) {
-    gb::set_error("gb_kmer workspace: %s", hipGetErrorString(e));
-    delete W;
-    return GB_ERR_HIP;
-  }
-  *out = W;
-  return GB_OK;
-}
-
-int budget_bytes(const char *who, int64_t *out) {
-  *out = kDefaultBudget;
-  const char *e = getenv("GB_KMER_WS");
-  if (!e || !*e) return GB_OK;
-  char *end = nullptr;
-  const long long v = strtoll(e, &end, 10);
-  GB_ARG(end && !*end && v > 0, "%s: GB_KMER_WS is '%s' (need a number of bytes > 0)", who, e);
-  *out = v;
-  return GB_OK;
-}
-bool host_path() {
-  const char *he = getenv("GB_KMER_HOST");
-  return he && *he == '1';
-}
+struct Ws : gb::WsBase<5> {};  // the calling thread's, through gb::get_ws
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int blocks(int64_t n) { return (int)ceil_div(n, kThreads); }
@@ -552,7 +505,7 @@ int count_device(const char *who, gb_kmer_counts *h, const uint8_t *bytes, int64
   int st;
   GB_HIP(hipGetDevice(&h->dev));
   Ws *W = nullptr;
-  if ((st = gb::thread_ws(h->dev, &W, make_ws))) return st;
+  if ((st = gb::get_ws("gb_kmer", h->dev, &W))) return st;
   hipStream_t s = W->stream;
   const int64_t n = h->n_occ, n_seqs = h->n_seqs, n_words = h->word_off[(size_t)n_seqs], tiles = tiles_of(n);
   Stats &S = stats();
@@ -719,13 +672,13 @@ int index_device(const char *who, gb_kmer_counts *h, gb_kmer_idx *x, int32_t min
   GB_ARG(dev == h->dev, "%s: the counts live on device %d and the current device is %d", who, h->dev, dev);
   const int64_t n = h->n_occ, n_seqs = h->n_seqs, nd = h->n_distinct, tiles = tiles_of(n);
   int64_t budget = 0;
-  if ((st = budget_bytes(who, &budget))) return st;
+  if ((st = gb::env_number(who, "GB_KMER_WS", 1, INT64_MAX, kDefaultBudget, &budget))) return st;
   const int64_t need = index_ws_bytes(n, n_seqs);
   GB_ARG(need <= budget, "%s: the index of %lld occurrences needs %lld bytes of device workspace, above the budget of %lld (GB_KMER_WS)",
          who, (long long)n, (long long)need, (long long)budget);
   if ((st = mirror(h))) return st;
   Ws *W = nullptr;
-  if ((st = gb::thread_ws(dev, &W, make_ws))) return st;
+  if ((st = gb::get_ws("gb_kmer", dev, &W))) return st;
   hipStream_t s = W->stream;
   Stats &S = stats();
   S.ws_bytes = need;
@@ -872,13 +825,13 @@ int gb_kmer_count(int k, const uint8_t *bytes, int64_t n_bytes, const int64_t *s
     const int64_t calls = S.calls;
     if (h->n_occ == 0) {
       S = Stats{};
-    } else if (host_path()) {
+    } else if (gb::env_flag("GB_KMER_HOST")) {
       S = Stats{};
       st = count_host(who, h, bytes + seq_off[0]);
     } else {
       const int64_t span = seq_off[n_seqs] - seq_off[0], need = count_ws_bytes(h->n_occ, span);
       int64_t budget = 0;
-      if (!(st = budget_bytes(who, &budget)) && need > budget) {
+      if (!(st = gb::env_number(who, "GB_KMER_WS", 1, INT64_MAX, kDefaultBudget, &budget)) && need > budget) {
         gb::set_error("%s: %lld occurrences need %lld bytes of device workspace, above the budget of %lld (GB_KMER_WS)",
                       who, (long long)h->n_occ, (long long)need, (long long)budget);
         st = GB_ERR_ARG;

@@ -1,6 +1,9 @@
 // gb_common.cpp -- error state and device selection shared by every gb_* entry point.
 #include "gb_common.h"
 
+#include <cerrno>
+#include <cstdlib>
+
 #include "../../include/gb.h"
 
 namespace gb {
@@ -15,6 +18,24 @@ void set_error(const char *fmt, ...) {
   g_err = buf;
 }
 const char *last_error() { return g_err.c_str(); }
+
+int env_number(const char *who, const char *name, int64_t lo, int64_t hi, int64_t dflt, int64_t *out) {
+  *out = dflt;
+  const char *e = getenv(name);
+  if (!e || !*e) return GB_OK;
+  char *end = nullptr;
+  errno = 0;
+  const long long v = strtoll(e, &end, 10);
+  GB_ARG(end != e && !*end && errno != ERANGE && v >= lo && v <= hi, "%s: %s is '%s' (need a number in %lld..%lld)", who,
+         name, e, (long long)lo, (long long)hi);
+  *out = v;
+  return GB_OK;
+}
+
+bool env_flag(const char *name) {
+  const char *e = getenv(name);
+  return e && *e == '1';
+}
 
 int thread_count(const char *who, const char *env_name, int *n) {
   int nth = 16;

@@ -1,8 +1,10 @@
 // gb_common.h -- shared host-side plumbing for the C ABI: error state, HIP checks, owning buffers and
-// handles, per-thread workspaces, host fork-join.
+// handles, per-thread workspaces and their maker, environment numbers and switches, the chunk cutter,
+// host fork-join.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -188,6 +190,115 @@ int thread_ws(int dev, int slot, T **out, Make &&make) {
 template <typename T, typename Make>
 int thread_ws(int dev, T **out, Make &&make) {
   return thread_ws<T>(dev, 0, out, make);
+}
+
+// What most legs' workspaces start with, and their maker: the calling thread's Ws (a WsBase) for dev
+// through thread_ws. First use sets the device and its CU count, creates the stream and the events,
+// and then runs the leg's own extra(W). extra returns a status whose error it has worded itself (a
+// reserve, say), or HIP's status of more handles it created, worded here like that of the common
+// ones: "<what> workspace: <hip error>", `what` naming the entry point.
+template <int kEvents>
+struct WsBase {
+  int device = -1, num_cus = 0;  // both set by get_ws before anyone sees the workspace
+  Stream stream;
+  Event ev[kEvents];
+};
+inline int ws_status(const char *, int st) { return st; }
+inline int ws_status(const char *what, hipError_t e) {
+  if (e == hipSuccess) return GB_OK;
+  set_error("%s workspace: %s", what, hipGetErrorString(e));
+  return GB_ERR_HIP;
+}
+template <typename Ws, typename Extra>
+int get_ws(const char *what, int dev, Ws **out, Extra &&extra) {
+  return thread_ws(dev, out, [&](int dev, Ws **out) -> int {
+    auto *W = new Ws();
+    W->device = dev;
+    hipError_t e = hipDeviceGetAttribute(&W->num_cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = W->stream.create();
+    for (auto &ev : W->ev)
+      if (e == hipSuccess) e = ev.create();
+    int st = ws_status(what, e);
+    if (!st) st = ws_status(what, extra(W));
+    if (st) {
+      delete W;
+      return st;
+    }
+    *out = W;
+    return GB_OK;
+  });
+}
+template <typename Ws>
+int get_ws(const char *what, int dev, Ws **out) {
+  return get_ws(what, dev, out, [](Ws *) -> int { return GB_OK; });
+}
+
+// For the accessors (`fn`) of an entry point (`call`): the calling thread's workspace on its current
+// device, or GB_ERR_STATE when call has not run there. With `ran`, a counter of the workspace such as
+// &Ws::calls, a workspace whose counter is 0 has not run either.
+template <typename Ws>
+int ran_ws(const char *fn, const char *call, const Ws **out, int64_t Ws::*ran = nullptr) {
+  int dev = 0;
+  GB_HIP(hipGetDevice(&dev));
+  const Ws *W = find_thread_ws<Ws>(dev);
+  if (!W || (ran && !(W->*ran))) {
+    set_error("%s: %s has not run on this thread and device", fn, call);
+    return GB_ERR_STATE;
+  }
+  *out = W;
+  return GB_OK;
+}
+
+// The whole decimal number in the environment variable `name`, read on every call: unset or empty is
+// dflt; anything but a number in [lo, hi] (text after it, nothing at all, out of int64_t's range) is
+// GB_ERR_ARG with "<who>: <name> is '<text>' ..." and leaves *out at dflt.
+int env_number(const char *who, const char *name, int64_t lo, int64_t hi, int64_t dflt, int64_t *out);
+// A switch such as GB_POA_HOST, read on every call: on exactly when the value begins with '1'.
+bool env_flag(const char *name);
+
+// A call cut to fit device memory. An item's need is a small struct of the leg's own: counts per
+// buffer with bytes(), += and, for largest(), max_with() (the element-wise maximum). A chunk is the items
+// [first, last) of the call and the sum of their needs.
+template <typename Need>
+struct Chunk {
+  int64_t first, last;
+  Need need;
+};
+// Appends the chunks of items 0 .. n-1, need_of(k) being item k's need: the items in order, each
+// joining the current chunk unless that chunk has an item and the sum would pass the budget. An item
+// that alone passes the budget is still a chunk of its own; the first such item's index is returned,
+// -1 when there is none.
+template <typename Need, typename F>
+int64_t cut_chunks(int64_t n, int64_t budget, F &&need_of, std::vector<Chunk<Need>> *chunks) {
+  int64_t over = -1;
+  Chunk<Need> cur{0, 0, Need{}};
+  for (int64_t k = 0; k < n; ++k) {
+    const Need one = need_of(k);
+    if (over < 0 && one.bytes() > budget) over = k;
+    if (cur.last > cur.first && cur.need.bytes() + one.bytes() > budget) {
+      chunks->push_back(cur);
+      cur = Chunk<Need>{k, k, Need{}};
+    }
+    cur.last = k + 1, cur.need += one;
+  }
+  if (cur.last > cur.first) chunks->push_back(cur);
+  return over;
+}
+// The largest any chunk asks of each buffer, the most items and the most bytes of any chunk: buffers
+// reserved at these do not grow between the chunks of a call.
+template <typename Need>
+struct Largest {
+  Need need{};
+  int64_t count = 0, bytes = 0;
+};
+template <typename Need>
+Largest<Need> largest(const std::vector<Chunk<Need>> &chunks) {
+  Largest<Need> big;
+  for (const Chunk<Need> &c : chunks) {
+    big.need.max_with(c.need);
+    big.count = std::max(big.count, c.last - c.first), big.bytes = std::max(big.bytes, c.need.bytes());
+  }
+  return big;
 }
 
 // Host worker threads for a call: the count in the environment variable env_name (default 16, values

@@ -1,6 +1,7 @@
 // gb_common_wave.h -- wave64 DPP primitives shared by the kernels of every leg: inclusive scans, the
-// one-lane shift and the wave maximum. Device only. A scan's identity fills the lanes a DPP step has
-// no source for and is a template parameter: each kernel passes its own "minus infinity".
+// one-lane shift, the wave maximum and the workgroup-wide add scan. Device only. A scan's identity
+// fills the lanes a DPP step has no source for and is a template parameter: each kernel passes its
+// own "minus infinity".
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -53,6 +54,24 @@ __device__ __forceinline__ uint64_t wave_shr1(uint64_t v, uint64_t lane0) {
 template <int kIdentity>
 __device__ __forceinline__ int wave_max(int v) {
   return __builtin_amdgcn_readlane(scan_max<kIdentity>(v), 63);
+}
+
+// Exclusive add scan of v over the kThreads lanes of the workgroup, and the workgroup's total; lds has
+// kThreads / 64 ints. Every thread of the workgroup calls it.
+template <int kThreads>
+__device__ __forceinline__ int block_scan_excl(int v, int *total, int *lds) {
+  const int inc = scan_add(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 63) lds[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int i = 0; i < kThreads / 64; ++i) {
+    const int t = lds[i];
+    if (i < (int)(threadIdx.x >> 6)) base += t;
+    tot += t;
+  }
+  *total = tot;
+  return base + inc - v;
 }
 
 }  // namespace gb
