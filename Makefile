@@ -126,6 +126,8 @@ $(eval $(call SANITIZE_RULE,chain-extd2,chain_extd2_host_check,chain_extd2.hip))
 $(eval $(call SANITIZE_RULE,poa,poa_host_check,bsw_poa.hip))
 $(eval $(call SANITIZE_RULE,kmer,kmer_host_check,fmi_kmer.hip))
 $(eval $(call SANITIZE_RULE,dbg,dbg_host_check,fmi_dbg.hip))
+# the host steps of a PairHMM fill (pack, merge, plan) and the arena's layout
+$(eval $(call SANITIZE_RULE,phmm,phmm_host_check,phmm.hip))
 
 oracle:
 	$(MAKE) -s -C oracle all

@@ -41,21 +41,16 @@
 #include "../../include/gb_phmm.h"
 #include "gb_common.h"
 #include "gb_common_wave.h"
+#include "phmm_internal.h"
+
+using namespace gb::phmm;
 
 namespace {
 
-constexpr int kWave = 64;
-// Longest haplotype a stack keeps in LDS: the f64 kernel's LDS (16-B boundary record + 1 code byte
-// per column, plus kBndPad + kWave pad columns) must fit the 160 KB of one CU. Stacks of longer
-// haplotypes (up to kMaxHaplen, the 16-bit field of TcDesc::dims) keep the same records in a global
-// scratch area per workgroup instead (phmm_forward<.., kLong>): the reference GKL has no cap.
-constexpr int kLdsHaplen = 9400;
-constexpr int kMaxHaplen = 65535;
 constexpr int kBndPad = 72;  // boundary records beyond column C (see phmm_stripe reads)
 constexpr int kRecPad = 16;  // boundary records below column 0 (phmm_stripe's lane 63 writes from column -2 on,
                              // phmm_rolled's from column -(kRollGroup - 1))
 constexpr int kQualTab = 128;
-constexpr int kStackRows = 2048;  // rows per stack (a testcase taller than this gets its own)
 // the batch's device counter words (d_count): [0..7] the passes' counters, then the f64 plan's
 // bucket counts, bucket cursors and its number of units with work (f64_plan)
 constexpr int kPlanBuckets = 128;
@@ -66,7 +61,6 @@ constexpr int kCountWords = kPlanTotal + 8;
 constexpr int kPredSampled = kPlanTotal + 1, kPredSamplePred = kPlanTotal + 2, kPredPredicted = kPlanTotal + 3;
 constexpr int kPredConfirmed = kPlanTotal + 4, kPredRedone = kPlanTotal + 5;
 static_assert(kPredRedone < kCountWords, "counter words");
-constexpr int kMaxF64Parts = 8;
 constexpr int kM2M = ((127 * 128) >> 1) + 128;  // set_mm_prob indices for quals < 128
 
 // ---------------------------------------------------------------------------------------------
@@ -155,7 +149,6 @@ static uint8_t read_match_mask(uint8_t rc) { return rc == 4 ? 0x1F : (uint8_t)((
 // shared between haplotypes does not know) yet leaks into the row below. A read may exit when
 // G <= kExitGrowthMax; the pack sets kMayExit in every row's match mask then.
 constexpr double kExitGrowthMax = 2.0;
-constexpr uint8_t kMayExit = 0x80;
 static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R) {
   const double inf = std::numeric_limits<double>::infinity();
   double G = 1.0;
@@ -197,7 +190,6 @@ static double exit_growth(const HostTables<float> &t, const uint8_t *rec, int R)
 // haplotype the read meets. log(rho), rounded up to f32, follows the read's five byte rows in the pool, and
 // verify_unit computes the testcase's own K from it.
 constexpr double kCertMax = 2.0;
-constexpr uint8_t kMayPredict = 0x80;
 // CertTab: per quality value the largest f32 / f64 ratio of the entries a row takes with it (+inf for an
 // entry that is 0 in f64 and positive in f32), so that a row costs five lookups at pack time.
 struct CertTab {
@@ -236,13 +228,6 @@ __host__ __device__ inline double cert_K(double log_rho, int R, int C) {
 // ---------------------------------------------------------------------------------------------
 // Device side
 // ---------------------------------------------------------------------------------------------
-struct __attribute__((aligned(16))) TcDesc {
-  uint32_t read_off;  // pool offset: rmatch[R] (| kMayExit) q[R] i[R] d[R] c[R]
-  uint32_t hap_off;   // pool offset: hcode[C]
-  uint32_t dims;      // rslen | haplen << 16
-  uint32_t out_idx;   // position in the caller's testcase array
-};
-
 template <typename T>
 struct DevTab {
   const T *ph2pr, *one_minus, *div3, *m2m;
@@ -498,12 +483,6 @@ __device__ __forceinline__ void load_row(const uint8_t *__restrict__ rbase, int 
 //       z = (M*pGAPM + X*0) + 0*0 = init_Y*pGAPM (the reference's (0*pMM + 0*pGAPM) + init_Y*pGAPM)
 //       and w = 0 (its 0*pMX + 0*pXX), zero before column 0.
 // Lanes beyond the stack's last row compute zeros.
-struct __attribute__((aligned(16))) Stack {
-  uint32_t first;  // first entry in the stack's testcase index list
-  uint32_t count;  // testcases (<= 64)
-  uint32_t hap_off;
-  uint32_t C;
-};
 struct __attribute__((aligned(16))) StackEnt {
   int start;  // stacked row of the testcase's first virtual row
   int R;
@@ -549,18 +528,7 @@ struct __attribute__((aligned(16))) StackEnt {
 // the next turn has reached column C then (P > 63), so nothing of the dying testcase has been
 // stored: the rows in flight are abandoned and the sweep starts again at the next testcase's first
 // row, a va row, which ignores the records it is handed.
-constexpr int kRollGroup = 16;
-
-// wave steps of a stack (or an f64 work unit) of `rows` stacked rows over C columns with stripes of
-// `sh` rows: the rolled sweep where phmm_stack takes it, else a fill per stripe
-__host__ __device__ inline uint64_t stack_steps(int rows, int C, int sh, bool roll) {
-  const int turns = (rows + sh - 1) / sh;
-  if (roll && sh == kWave && C >= kWave && C <= kLdsHaplen && turns >= 2) {
-    const int P = (C + kRollGroup + 1 + 3) & ~3;
-    return (uint64_t)(turns - 1) * (uint64_t)P + (uint64_t)(C + rows - kWave * (turns - 1));
-  }
-  return (uint64_t)turns * (uint64_t)(C + sh);
-}
+// (kRollGroup and the sweeps' cost in wave steps, stack_steps: phmm_internal.h)
 
 // The rolled sweep of a stack's rows from `base` (at least two turns, C >= 64). Returns the stacked
 // row the stack goes on from: T_rows, or the next testcase's first row after an early exit.
@@ -620,7 +588,7 @@ __device__ __forceinline__ int phmm_rolled(const int base, const int T_rows, con
     return D;
   };
   // The switch proper: the lanes in `mine` take their row's constants (the table entries load_row reads)
-  // and initial state (setup_row's, for a row that does not start at column 1), in place.
+  // and initial state (phmm_stack's, for a row that does not start at column 1), in place.
   auto expand = [&](const RowDesc &D, bool mine, RowParams<T> &P, LaneState<T> &st) {
     if (mine) {
       const T zero = (T)0, one = (T)1;
@@ -1002,238 +970,6 @@ __device__ __forceinline__ int phmm_stack(const Stack &S, const uint32_t *__rest
   return na;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Two rows per lane (the f32 pass over LDS stacks). A stripe is 128 rows: lane k owns rows 2k (a)
-// and 2k+1 (b), and row rho of the stripe is at column t - rho + 1 at step t, as before. Row b runs
-// one column behind row a in the same lane, so its inputs from the row above (X = w and the bracket
-// z of row a) are row a's previous-step values, carried in registers; only row a's inputs cross a
-// lane (lane k-1's row b, DPP wave_shr). Per two cells: 24 FP ops, 2 DPP moves, 2 selects, one LDS
-// code read (row b reuses row a's code of the step before) -- against 2 DPP moves and 2 code reads
-// per two cells with one row per lane. The arithmetic of each cell is unchanged (same operands,
-// same order), so the results are bit-identical.
-constexpr int kRows2 = 2 * kWave;  // stripe height
-constexpr int kBndPad2 = 136;      // records / codes beyond column C (lane 0 reads up to C + kRows2 + 2)
-constexpr int kCodePad2 = kRows2;  // codes below column 0 (lane 63's row a starts at column -125)
-constexpr int kNoWrite2 = kRows2 - 4;  // lane 63's row b writes from column -2 on (step 124)
-
-// One row's constants and initial state (phmm_stack's per-lane set-up, for stripe row rho): r is the
-// row's place in its testcase (0: va, 1: v0, 2..R+1: read row r-2); z_top the bracket lane 0's first
-// row takes from the record at column 0.
-template <typename T>
-__device__ __forceinline__ void setup_row(int rho, bool dead, int r, int R, const uint8_t *__restrict__ rbase,
-                                          const DevTab<T> &tab, T init_Y, T z_top, RowParams<T> &P,
-                                          LaneState<T> &st) {
-  st.Mp = st.zo = st.wo = (T)0;
-  st.Yp = (T)0;
-  st.zd = rho == 0 ? z_top : (T)0;
-  T pMM, pGAPM, pMX, pXX, a, b, dm, dx;
-  uint32_t f;
-  const T zero = (T)0, one = (T)1;
-  P.nMM = P.nGAPM = P.nGAPMx = P.nMX = P.nXX = zero;
-  if (dead) {
-    P.pMY = P.pYY = P.dmatch = P.dmis = zero;
-    P.rmask = 0;
-  } else if (r == 0) {  // va
-    P.pMY = zero;
-    P.pYY = one;
-    P.dmatch = P.dmis = zero;
-    P.rmask = 0;
-    P.nGAPM = one;
-    st.Yp = init_Y;
-    st.zo = (zero * zero + zero * zero) + init_Y * one;
-  } else if (r == 1) {  // v0
-    P.pMY = P.pYY = zero;
-    P.dmatch = one;
-    P.dmis = zero;
-    P.rmask = 0x3F;
-    load_row(rbase, R, 0, tab, pMM, pGAPM, pMX, pXX, a, b, dm, dx, f);
-    P.nMM = pGAPM;
-    st.zd = init_Y;
-    if (rho == 0) st.zo = (init_Y * P.nMM + zero * zero) + zero * zero;
-  } else {
-    load_row(rbase, R, r - 2, tab, pMM, pGAPM, pMX, pXX, P.pMY, P.pYY, P.dmatch, P.dmis, P.rmask);
-    if (r - 1 < R) {
-      load_row(rbase, R, r - 1, tab, P.nMM, P.nGAPM, P.nMX, P.nXX, a, b, dm, dx, f);
-      P.nGAPMx = P.nGAPM;
-    }
-  }
-}
-
-// One step of both rows: row b (column c - 1) from row a's previous-step partials, row a (column c)
-// from lane k-1's row b (previous step) or, in lane 0, the record of the stripe above.
-template <typename T, bool kSum, bool kWrite>
-__device__ __forceinline__ void phmm_step2(const Brec<T> &rec, uint32_t h, uint32_t &hb, LaneState<T> &A,
-                                           LaneState<T> &B, const RowParams<T> &PA, const RowParams<T> &PB,
-                                           T &sMa, T &sXa, T &sMb, T &sXb, Brec<T> *wr, bool last_lane) {
-  const T Xb = A.wo;
-  const T zdnb = A.zo;
-  const T Xa = dpp<gb::wave_shr1>(B.wo, rec.w);
-  const T zdna = dpp<gb::wave_shr1>(B.zo, rec.z);
-  const T Mb = B.zd * select_dist(PB.rmask, hb, PB.dmatch, PB.dmis);
-  const T Ma = A.zd * select_dist(PA.rmask, h, PA.dmatch, PA.dmis);
-  const T Yb = B.Mp * PB.pMY + B.Yp * PB.pYY;
-  const T Ya = A.Mp * PA.pMY + A.Yp * PA.pYY;
-  B.zo = (Mb * PB.nMM + Xb * PB.nGAPMx) + Yb * PB.nGAPM;
-  B.wo = Mb * PB.nMX + Xb * PB.nXX;
-  A.zo = (Ma * PA.nMM + Xa * PA.nGAPMx) + Ya * PA.nGAPM;
-  A.wo = Ma * PA.nMX + Xa * PA.nXX;
-  if constexpr (kSum) {
-    sMa = sMa + Ma;
-    sXa = sXa + Xa;
-    sMb = sMb + Mb;
-    sXb = sXb + Xb;
-  }
-  if constexpr (kWrite) {
-    if (last_lane) {
-      Brec<T> r;
-      r.z = B.zo;
-      r.w = B.wo;
-      *wr = r;
-    }
-  }
-  A.zd = zdna;
-  A.Mp = Ma;
-  A.Yp = Ya;
-  B.zd = zdnb;
-  B.Mp = Mb;
-  B.Yp = Yb;
-  hb = h;
-}
-
-// Sweep `steps` anti-diagonals of a 128-row stripe, 4 per iteration. Last rows: row rho of the stripe
-// reaches column C at step C + rho - 1, where its sum is final (pa: rows a by lane, pb: rows b).
-template <typename T, bool kSum, bool kWrite>
-__device__ __forceinline__ void phmm_stripe2(int steps, LaneState<T> &A, LaneState<T> &B, const RowParams<T> &PA,
-                                             const RowParams<T> &PB, Brec<T> *__restrict__ bnd,
-                                             const uint8_t *__restrict__ hcol, int C, int lane, uint64_t pa,
-                                             uint64_t pb, T *__restrict__ outA, T *__restrict__ outB) {
-  const uint8_t *hl = hcol + 1 - 2 * lane;
-  const bool last_lane = lane == kWave - 1;
-  constexpr int U = 4;
-  T sMa = (T)0, sXa = (T)0, sMb = (T)0, sXb = (T)0;
-  uint32_t hb = hl[-1];  // row b's code at its column before step 0
-  auto next_target = [&]() -> int {
-    if (!kSum || !(pa | pb)) return INT_MAX;
-    const int ra = pa ? 2 * __builtin_ctzll(pa) : INT_MAX / 2;
-    const int rb = pb ? 2 * __builtin_ctzll(pb) + 1 : INT_MAX / 2;
-    return C + min(ra, rb) - 1;
-  };
-  int target = next_target();
-  auto single = [&](int tt, auto wr_tag) {
-    constexpr bool W = decltype(wr_tag)::value;
-    phmm_step2<T, kSum, W>(bnd[tt + 1], hl[tt], hb, A, B, PA, PB, sMa, sXa, sMb, sXb, bnd + (tt - (kRows2 - 2)),
-                           last_lane);
-    if (kSum && tt == target) {
-      const int rho = tt - C + 1;
-      if (rho & 1) {
-        if (lane == (rho >> 1)) *outB = sMb + sXb;
-        pb &= pb - 1;
-      } else {
-        if (lane == (rho >> 1)) *outA = sMa + sXa;
-        pa &= pa - 1;
-      }
-      target = next_target();
-    }
-  };
-  int vzero;
-  asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-  Brec<T> *wb = bnd - (kRows2 - 2) + vzero;
-  auto run = [&](int t, int end, auto wr_tag) {
-    constexpr bool W = decltype(wr_tag)::value;
-    for (; t + U <= end; t += U) {
-      if (kSum && target < t + U) {
-        for (int u = 0; u < U; u++) single(t + u, wr_tag);
-        continue;
-      }
-      Brec<T> *wr = wb + t;
-      const Brec<T> c0 = wr[kRows2 - 1], c1 = wr[kRows2], c2 = wr[kRows2 + 1], c3 = wr[kRows2 + 2];
-      const uint32_t h0 = hl[t], h1 = hl[t + 1], h2 = hl[t + 2], h3 = hl[t + 3];
-      phmm_step2<T, kSum, W>(c0, h0, hb, A, B, PA, PB, sMa, sXa, sMb, sXb, wr, last_lane);
-      phmm_step2<T, kSum, W>(c1, h1, hb, A, B, PA, PB, sMa, sXa, sMb, sXb, wr + 1, last_lane);
-      phmm_step2<T, kSum, W>(c2, h2, hb, A, B, PA, PB, sMa, sXa, sMb, sXb, wr + 2, last_lane);
-      phmm_step2<T, kSum, W>(c3, h3, hb, A, B, PA, PB, sMa, sXa, sMb, sXb, wr + 3, last_lane);
-    }
-    for (; t < end; t++) single(t, wr_tag);
-  };
-  if constexpr (kWrite) {
-    const int a = min(steps, kNoWrite2);
-    run(0, a, std::false_type{});
-    run(a, steps, std::true_type{});
-  } else {
-    run(0, steps, std::false_type{});
-  }
-}
-
-// phmm_stack with two rows per lane (f32 pass, every testcase of the stack).
-template <typename T>
-__device__ __forceinline__ void phmm_stack2(const Stack &S, const uint32_t *__restrict__ stk_tc,
-                                            const TcDesc *__restrict__ descs, const uint8_t *__restrict__ pool,
-                                            const DevTab<T> &tab, T *__restrict__ raw_out, uint8_t *smem_raw) {
-  const int lane = threadIdx.x;
-  const int C = (int)S.C;
-  Brec<T> *bnd = reinterpret_cast<Brec<T> *>(smem_raw) + kRecPad;
-  uint8_t *hcol = smem_raw + sizeof(Brec<T>) * (size_t)(C + kBndPad2 + kRecPad) + kCodePad2;
-  const int na = (int)S.count;
-  TcDesc d = {0, 0, 0, 0};
-  if (lane < na) d = descs[stk_tc[S.first + lane]];
-  const int rows = lane < na ? (int)(d.dims & 0xffff) + 2 : 0;
-  const int incl = gb::scan_add(rows);
-  const int T_rows = __builtin_amdgcn_readlane(incl, 63);
-  const int e_start = incl - rows, e_R = rows - 2;  // entry a in lane a
-  const T init_Y = tab.init_const / (T)C;
-  const uint8_t *hcode = pool + S.hap_off;
-  for (int c = lane; c < C + kBndPad2; c += kWave) {
-    Brec<T> b;
-    b.z = (T)0;
-    b.w = (T)0;
-    bnd[c] = b;
-  }
-  for (int c = lane - kCodePad2; c < C + kBndPad2; c += kWave)
-    hcol[c] = (c >= 1 && c <= C) ? hcode[c - 1] : (c == 0 ? 5 : (c < 0 ? 6 : 0));
-  __syncthreads();
-
-  const int nstripes = (T_rows + kRows2 - 1) / kRows2;
-  for (int s = 0; s < nstripes; s++) {
-    const int g0 = s * kRows2 + 2 * lane, g1 = g0 + 1;
-    int lo = 0, hi = na - 1;
-    while (__builtin_amdgcn_ballot_w64(lo < hi)) {
-      const int mid = (lo + hi + 1) >> 1;
-      const int sm = __shfl(e_start, mid);
-      if (lo < hi) {
-        if (sm <= g0) lo = mid; else hi = mid - 1;
-      }
-    }
-    // row b: the same testcase, or the next one when it starts at g1
-    const int nxt = __shfl(e_start, min(lo + 1, kWave - 1));
-    const int lob = (lo + 1 < na && nxt <= g1) ? lo + 1 : lo;
-    const int sa = __shfl(e_start, lo), Ra = __shfl(e_R, lo);
-    const uint32_t rda = (uint32_t)__shfl((int)d.read_off, lo), oa = (uint32_t)__shfl((int)d.out_idx, lo);
-    const int sb = __shfl(e_start, lob), Rb = __shfl(e_R, lob);
-    const uint32_t rdb = (uint32_t)__shfl((int)d.read_off, lob), ob = (uint32_t)__shfl((int)d.out_idx, lob);
-    const int ra = g0 - sa, rb = g1 - sb;
-    const bool deadA = g0 >= T_rows, deadB = g1 >= T_rows;
-    RowParams<T> PA, PB;
-    LaneState<T> A, B;
-    const T z_top = lane == 0 ? bnd[0].z : (T)0;
-    setup_row<T>(2 * lane, deadA, ra, Ra, pool + rda, tab, init_Y, z_top, PA, A);
-    setup_row<T>(2 * lane + 1, deadB, rb, Rb, pool + rdb, tab, init_Y, (T)0, PB, B);
-    const uint64_t pa = __builtin_amdgcn_ballot_w64(!deadA && ra == Ra + 1);
-    const uint64_t pb = __builtin_amdgcn_ballot_w64(!deadB && rb == Rb + 1);
-    const bool more = s < nstripes - 1;
-    const int steps = more ? C + kRows2 - 1 : C + (T_rows - s * kRows2) - 1;
-    T *outA = raw_out + oa, *outB = raw_out + ob;
-    if (pa | pb) {
-      if (more)
-        phmm_stripe2<T, true, true>(steps, A, B, PA, PB, bnd, hcol, C, lane, pa, pb, outA, outB);
-      else
-        phmm_stripe2<T, true, false>(steps, A, B, PA, PB, bnd, hcol, C, lane, pa, pb, outA, outB);
-    } else {
-      phmm_stripe2<T, false, true>(steps, A, B, PA, PB, bnd, hcol, C, lane, 0, 0, outA, outB);
-    }
-    __syncthreads();
-  }
-}
-
 // cert_K as a call: inlined into the f64 pass's persistent loop, exp's polynomial constants are hoisted
 // out of that loop into 28 registers that live through the f64 sweeps, which have 21 to spare
 __device__ __attribute__((noinline)) double cert_K_call(double log_rho, int R, int C) { return cert_K(log_rho, R, C); }
@@ -1274,18 +1010,6 @@ __device__ __forceinline__ bool verify_unit(const Stack &S, int part, int parts,
   }
   nre += __builtin_popcountll(rem);
   return rem != 0;
-}
-
-// W: the waves per SIMD the register allocation is held to (0: the compiler's own choice)
-template <int W>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W ? W : 1, 8))) void phmm_forward2(
-                                                     const Stack *__restrict__ stacks,
-                                                     const uint32_t *__restrict__ stk_tc,
-                                                     const TcDesc *__restrict__ descs,
-                                                     const uint8_t *__restrict__ pool, DevTab<float> tab,
-                                                     float *__restrict__ raw_out) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  phmm_stack2<float>(stacks[blockIdx.x], stk_tc, descs, pool, tab, raw_out, smem_raw);
 }
 
 // f32 pass: one stack per workgroup (LPT order). f64 pass: a persistent grid takes stacks through
@@ -1636,9 +1360,20 @@ __global__ void phmm_finalize(const float *__restrict__ rf, double *__restrict__
   out[i] = (rf[i] < 1e-28f) ? (log10(rd[i]) - log10_init_d) : (double)(log10f(rf[i]) - log10_init_f);
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------------------------------------
 // Host state
 // ---------------------------------------------------------------------------------------------
+// The host tables, built once (ensure_host_tables); the pack reads hf and cert.
+struct gb::phmm::PackTables {
+  HostTables<float> hf;
+  HostTables<double> hd;
+  CertTab cert;
+};
+
+namespace {
+
 struct DeviceTables {
   int device = -1;
   float *f = nullptr;   // ph2pr | one_minus | div3 | m2m
@@ -1648,22 +1383,16 @@ struct DeviceTables {
 };
 
 std::mutex g_mu;
-HostTables<float> *g_hf = nullptr;
-HostTables<double> *g_hd = nullptr;
-CertTab *g_cert = nullptr;
+PackTables *g_host = nullptr;
 std::unordered_map<int, DeviceTables *> g_dev;
 
 int ensure_host_tables() {
-  if (!g_hf) {
-    auto *f = new HostTables<float>();
-    auto *d = new HostTables<double>();
-    build_tables(*f);
-    build_tables(*d);
-    auto *c = new CertTab();
-    build_cert_tab(*f, *d, *c);
-    g_cert = c;
-    g_hf = f;
-    g_hd = d;
+  if (!g_host) {
+    auto *t = new PackTables();
+    build_tables(t->hf);
+    build_tables(t->hd);
+    build_cert_tab(t->hf, t->hd, t->cert);
+    g_host = t;
   }
   return GB_OK;
 }
@@ -1696,14 +1425,14 @@ int get_device_tables(DeviceTables **out) {
   }
   auto *t = new DeviceTables();
   t->device = dev;
-  t->hf = *g_hf;
-  t->hd = *g_hd;
-  int st = upload_tables(*g_hf, &t->f);
+  t->hf = g_host->hf;
+  t->hd = g_host->hd;
+  int st = upload_tables(g_host->hf, &t->f);
   if (st) return st;
-  st = upload_tables(*g_hd, &t->d);
+  st = upload_tables(g_host->hd, &t->d);
   if (st) return st;
   for (auto fn : {(const void *)phmm_forward<float, false>, (const void *)phmm_forward<float, false, false, true>,
-                  (const void *)phmm_forward<double, true>, (const void *)phmm_forward2<0>, (const void *)phmm_forward2<6>, (const void *)phmm_forward2<8>})
+                  (const void *)phmm_forward<double, true>})
     GB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   g_dev[dev] = t;
   *out = t;
@@ -1718,11 +1447,6 @@ struct ReadKey {
   bool operator==(const ReadKey &o) const {
     return rs == o.rs && q == o.q && i == o.i && d == o.d && c == o.c && len == o.len;
   }
-};
-struct HapKey {
-  const char *h;
-  int len;
-  bool operator==(const HapKey &o) const { return h == o.h && len == o.len; }
 };
 struct KeyHash {
   size_t mix(size_t a, size_t b) const { return a ^ (b + 0x9e3779b97f4a7c15ull + (a << 6) + (a >> 2)); }
@@ -1739,8 +1463,8 @@ struct KeyHash {
 
 struct gb_phmm_batch {
   DeviceTables *tabs = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  gb::Stream stream;
+  gb::Event ev[4];
   int n = 0;
   int max_haplen = 0;
   int64_t cells = 0;
@@ -1768,13 +1492,7 @@ struct gb_phmm_batch {
   int cus = 256;                   // compute units of the device (stack height rule)
   bool ran = false;
   bool force_f64 = false;
-  int rpl = 1;  // rows per lane of the f32 pass over LDS stacks (GB_PHMM_RPL=2: two, for A/B probes)
-  int w2 = 0;   // its register budget: waves per SIMD 0 (compiler), 6 or 8 (GB_PHMM_W2, probes)
-  int f64_parts = 2;  // work units per stack in the f64 pass (GB_PHMM_F64_PARTS)
-  bool f64_plan = true;  // the f64 pass's units by cost (f64_plan; GB_PHMM_F64_PLAN=0: stack order)
-  bool f32_exit = true;  // the f32 pass's early exit (phmm_stack kExit; GB_PHMM_EXIT=0 turns it off)
-  bool roll = true;      // both passes' rolled sweep of the LDS stacks (phmm_rolled; GB_PHMM_ROLL=0: a fill per stripe)
-  int predict = 1;       // the fallback predictor (phmm_predict; GB_PHMM_PREDICT=0: off, all: every certified testcase, open: no gate)
+  Knobs knobs;  // the last fill's (read_knobs); the launches read f64_parts, f64_plan, f32_exit, roll and predict
   bool resident = false;  // made by gb_phmm_batch_create (packed once, run many times), not a one-shot workspace
   bool gate_open = false; // batch_fill's sample: enough of the batch is predicted for the predictor to run
   int gate_n = 0, gate_pred = 0;  // the sample's testcases and predictions
@@ -1805,32 +1523,13 @@ int gb_phmm_init(void) {
 
 namespace {
 
-// GB_PHMM_HOSTPROF=1: host phase times of the drop-in path on stderr (development aid)
-struct HostClock {
-  bool on;
-  std::chrono::steady_clock::time_point t0;
-  HostClock() : on(getenv("GB_PHMM_HOSTPROF") != nullptr), t0(std::chrono::steady_clock::now()) {}
-  void mark(const char *what) {
-    if (!on) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[phmm host] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count());
-    t0 = t;
-  }
-};
-
 // Device buffers of a batch for n testcases and a pool of pool_bytes (grow-only). The pipelined path
 // reserves every chunk's buffers before its first launch: an allocation that grows a buffer frees
 // the old one, and hipFree waits for the device.
 int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
-  const size_t nn = std::max(n, 1);
-  auto up = [](size_t x) { return gb::round_up<size_t>(x, 256); };
-  const size_t sz[10] = {up(sizeof(TcDesc) * nn), up(sizeof(float) * nn), up(sizeof(double) * nn),
-                         up(sizeof(double) * nn), up(sizeof(uint32_t) * nn),
-                         up(sizeof(Stack) * nn),  // at most one stack per testcase
-                         up(sizeof(uint32_t) * nn * kMaxF64Parts), up(nn * kMaxF64Parts), up(nn), up(nn)};
-  const size_t arena = sz[0] + sz[1] + sz[2] + sz[3] + sz[4] + sz[5] + sz[6] + sz[7] + sz[8] + sz[9];
-  // every sz[] grows with nn, so an arena that holds this sum was carved for at least these sizes
-  if (arena > b->d_arena.capacity()) {
+  const ArenaLayout A = arena_layout(std::max(n, 1));
+  // every array grows with n, so an arena that holds this total was carved for at least these sizes
+  if (A.total > b->d_arena.capacity()) {
     // the per-testcase arrays carved from one allocation (a cold process pays per hipMalloc)
     b->d_desc = nullptr;
     b->d_rf = nullptr;
@@ -1840,28 +1539,19 @@ int batch_reserve(gb_phmm_batch *b, int n, size_t pool_bytes) {
     b->d_units = nullptr;
     b->d_ukey = nullptr;
     b->d_pred = b->d_redo = nullptr;
-    if (int st = b->d_arena.reserve(arena)) return st;
+    if (int st = b->d_arena.reserve(A.total)) return st;
     uint8_t *a = b->d_arena;
-    b->d_desc = (TcDesc *)a;
-    a += sz[0];
-    b->d_rf = (float *)a;
-    a += sz[1];
-    b->d_rd = (double *)a;
-    a += sz[2];
-    b->d_pred = a;  // d_rd, d_pred and d_redo are zeroed by one fill
-    a += sz[8];
-    b->d_redo = a;
-    a += sz[9];
-    b->pred_bytes = sz[2] + sz[8] + sz[9];
-    b->d_out = (double *)a;
-    a += sz[3];
-    b->d_stk_tc = (uint32_t *)a;
-    a += sz[4];
-    b->d_stacks = (Stack *)a;
-    a += sz[5];
-    b->d_units = (uint32_t *)a;
-    a += sz[6];
-    b->d_ukey = a;
+    b->d_desc = (TcDesc *)(a + A.desc);
+    b->d_rf = (float *)(a + A.rf);
+    b->d_rd = (double *)(a + A.rd);
+    b->d_pred = a + A.pred;
+    b->d_redo = a + A.redo;
+    b->pred_bytes = A.out - A.rd;  // d_rd, d_pred and d_redo are zeroed by one fill
+    b->d_out = (double *)(a + A.out);
+    b->d_stk_tc = (uint32_t *)(a + A.stk_tc);
+    b->d_stacks = (Stack *)(a + A.stacks);
+    b->d_units = (uint32_t *)(a + A.units);
+    b->d_ukey = a + A.ukey;
   }
   if (int st = b->d_pool.reserve(pool_bytes)) return st;
   return b->d_count.reserve(kCountWords);
@@ -1923,150 +1613,174 @@ int validate_testcases(const gb_testcase *tcs, int n) {
   return GB_OK;
 }
 
-// Pack the testcases (deduplicated reads/haplotypes, stacks in LPT order) into b's pinned staging
-// buffer and upload them, growing its buffers when they are too small; b's stream/events exist
-// already. threads: host threads of the pack and merge phases (0: up to 8 from pack_min testcases).
-// validated: the caller has run validate_testcases over the whole call (compute_pipelined, whose
-// chunks would otherwise name a testcase by its index in the chunk).
-int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0, bool validated = false) {
-  HostClock clk;
-  // Pack: deduplicate reads and haplotypes by pointer (the driver shares them across the R x H
-  // cross product, PairHMMUnitTest.cpp:564-579), convert bases to codes once. Inputs are validated
-  // first (sequentially, so the error names the first bad testcase), then big jobs pack in
-  // contiguous chunks on several threads, each with its own pool and maps; chunk pools are
-  // concatenated and haplotype ids are made global in first-appearance order, which is the id order
-  // a single pass gives (a read shared across a chunk edge is stored once per chunk). Descriptors,
-  // stack lists, stacks and pool are written straight into the pinned staging buffer.
-  if (!validated)
-    if (int st = validate_testcases(tcs, n)) return st;
-  clk.mark("validate");
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// A fill's host steps (phmm_internal.h): knobs, pack, merge, plan. No HIP call, no batch.
+// ---------------------------------------------------------------------------------------------
+namespace gb {
+namespace phmm {
+
+const PackTables &host_tables() {
+  std::lock_guard<std::mutex> lk(g_mu);
+  ensure_host_tables();
+  return *g_host;
+}
+
+Knobs read_knobs() {
+  Knobs K;
   // calls from 8 K testcases pack on several threads (2 K testcases each at least): the reference's
   // per-batch calls (PairHMMUnitTest.cpp:549-593) are mostly 5-45 K testcases
-  int pack_min = 1 << 13;  // GB_PHMM_PACK_MIN (probes): the smallest call packed on several threads
-  if (const char *e = getenv("GB_PHMM_PACK_MIN")) pack_min = std::max(1, atoi(e));
-  int nth = n >= pack_min ? (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
-  if (threads > 0) nth = std::max(1, std::min(threads, n / 4096));
-  nth = std::max(1, std::min(nth, n / 2048));
-  const size_t nn = std::max(n, 1);
-  host_reserve(b, nn, 0, nth);
-  // descriptors are written by the pack (a bigger pool than guessed grows the buffer after it)
-  if (int st = stage_reserve(b, StageLayout(nn, 32 * nn).total)) return st;
-  TcDesc *desc = (TcDesc *)b->h_stage.get();
-  uint32_t *hid = b->hid.data();  // dense haplotype index of each testcase (stack grouping)
-  struct Chunk {
-    int lo = 0, hi = 0;
-    std::vector<uint8_t> *pool = nullptr;
-    std::vector<uint32_t> hap_off;  // local haplotype id -> offset in this chunk's pool
-    std::vector<HapKey> hap_key;    // local haplotype id -> key
-    int64_t cells = 0;
+  if (const char *e = getenv("GB_PHMM_PACK_MIN")) K.pack_min = std::max(1, atoi(e));  // probes
+  // work units per stack in the f64 pass: in stack order, two units per stack took the 1/8 shard's
+  // f64 pass 2.28 -> 2.00 ms (profiles/r05e_phmm_f64_parts.log); ordered by cost (f64_plan) one unit
+  // per stack is best: the shard 1.93 (stack order, two) -> 1.82 (plan, two) -> 1.78 ms (plan, one), the
+  // whole job 13.19 -> 13.07 -> 12.95 ms (profiles/r06x_phmm_f64_plan.log)
+  if (const char *e = getenv("GB_PHMM_F64_PARTS")) K.f64_parts = std::max(1, std::min(kMaxF64Parts, atoi(e)));
+  if (const char *e = getenv("GB_PHMM_F64_PLAN")) K.f64_plan = atoi(e) != 0;
+  // the f32 pass drops a testcase's remaining rows once its crossing mass proves it falls back to f64
+  // (phmm_stack kExit): f32 pass 19.05 -> 18.40 ms, step +2.0 % (profiles/r05zzi_phmm_exit_ab.log);
+  // finals, raw f64 and the fallback choice unchanged, a dropped testcase's raw f32 reads 0
+  if (const char *e = getenv("GB_PHMM_EXIT")) K.f32_exit = atoi(e) != 0;
+  // rolled stripes (phmm_rolled) in both passes
+  if (const char *e = getenv("GB_PHMM_ROLL")) K.roll = atoi(e) != 0;
+  // the fallback predictor (phmm_predict): on; GB_PHMM_PREDICT=0 off, =all every certified testcase with
+  // the gate off (tests: every passing testcase then takes the verify -> redo path), =open the estimate
+  // with the gate off (tests of jobs too small for the gate's sample)
+  if (const char *e = getenv("GB_PHMM_PREDICT"))
+    K.predict = strcmp(e, "all") == 0 ? 2 : strcmp(e, "open") == 0 ? 3 : (atoi(e) != 0 ? 1 : 0);
+  if (const char *e = getenv("GB_PHMM_STACK_ROWS")) K.stack_rows_forced = std::max(1, atoi(e));  // probes
+  // GB_PHMM_TAIL=frac:rows (0 = off) for probes of plan_stacks' tail split
+  if (const char *te = getenv("GB_PHMM_TAIL")) {
+    K.tail_frac = std::max(0.0, atof(te));  // (anything not above 0 is off)
+    const char *cm = strchr(te, ':');
+    if (cm) K.tail_rows = std::max(1, atoi(cm + 1));
+  }
+  return K;
+}
+
+// One chunk of the pack. The reference driver's r-major loop repeats a read for every haplotype and cycles
+// the haplotypes: a last-read check and a small direct-mapped haplotype cache skip most hash lookups.
+static void pack_chunk(const gb_testcase *tcs, PackChunk &C, bool cert_wanted, const PackTables &tables,
+                       TcDesc *desc, uint32_t *hid) {
+  std::unordered_map<ReadKey, uint32_t, KeyHash> read_at;
+  std::unordered_map<HapKey, uint32_t, KeyHash> hap_at;
+  ReadKey last_rk{nullptr, nullptr, nullptr, nullptr, nullptr, -1};
+  uint32_t last_roff = 0;
+  struct HapSlot {
+    const char *h = nullptr;
+    int len = -1;
+    uint32_t id = 0;
   };
-  std::vector<Chunk> ch(nth);
-  // one-shot calls below kPredMinCells do without the predictor (phmm_predict, "Gate")
-  int64_t pre_cells = 0;
-  for (int k = 0; k < n; k++) pre_cells += (int64_t)tcs[k].rslen * tcs[k].haplen;
-  const bool cert_wanted = b->resident || pre_cells >= kPredMinCells;
-  auto pack_chunk = [&](Chunk &C) {
-    std::unordered_map<ReadKey, uint32_t, KeyHash> read_at;
-    std::unordered_map<HapKey, uint32_t, KeyHash> hap_at;
-    // the reference driver's r-major loop repeats a read for every haplotype and cycles the
-    // haplotypes: a last-read check and a small direct-mapped haplotype cache skip most hash lookups
-    ReadKey last_rk{nullptr, nullptr, nullptr, nullptr, nullptr, -1};
-    uint32_t last_roff = 0;
-    struct HapSlot {
-      const char *h = nullptr;
-      int len = -1;
-      uint32_t id = 0;
-    };
-    HapSlot hcache[256];
-    std::vector<uint8_t> &pool = *C.pool;
-    for (int k = C.lo; k < C.hi; k++) {
-      const gb_testcase &t = tcs[k];
-      const ReadKey rk{t.rs, t.q, t.i, t.d, t.c, t.rslen};
-      uint32_t roff;
-      if (rk == last_rk) {
-        roff = last_roff;
+  HapSlot hcache[256];
+  std::vector<uint8_t> &pool = *C.pool;
+  for (int k = C.lo; k < C.hi; k++) {
+    const gb_testcase &t = tcs[k];
+    const ReadKey rk{t.rs, t.q, t.i, t.d, t.c, t.rslen};
+    uint32_t roff;
+    if (rk == last_rk) {
+      roff = last_roff;
+    } else {
+      auto ri = read_at.find(rk);
+      if (ri != read_at.end()) {
+        roff = ri->second;
       } else {
-        auto ri = read_at.find(rk);
-        if (ri != read_at.end()) {
-          roff = ri->second;
-        } else {
-          roff = (uint32_t)pool.size();
-          pool.resize(pool.size() + 5 * (size_t)t.rslen + sizeof(float));  // and the certificate's log(rho)
-          uint8_t *rec = pool.data() + roff;
-          for (int r = 0; r < t.rslen; r++) {
-            rec[r] = read_match_mask(base_code(t.rs[r]));
-            rec[t.rslen + r] = (uint8_t)t.q[r];
-            rec[2 * t.rslen + r] = (uint8_t)t.i[r];
-            rec[3 * t.rslen + r] = (uint8_t)t.d[r];
-            rec[4 * t.rslen + r] = (uint8_t)t.c[r];
-          }
-          // the early exit's gate: bit 7 of every row's match mask (select_dist reads bits 0..6)
-          if (exit_growth(b->tabs->hf, rec, t.rslen) <= kExitGrowthMax)
-            for (int r = 0; r < t.rslen; r++) rec[r] |= kMayExit;
-          // the predictor's certificate: bit 7 of the first quality byte (the kernels read bits 0..6)
-          if (t.rslen > 0) rec[t.rslen] &= 127;
-          // (a call that will not be predicted, see may_predict below, certifies nothing)
-          const double lr = cert_wanted ? cert_log_rho(*g_cert, rec + t.rslen, rec + 2 * t.rslen, rec + 3 * t.rslen,
-                                                       rec + 4 * t.rslen, t.rslen)
-                                        : std::numeric_limits<double>::infinity();
-          float lrf = 0.f;
-          if (t.rslen > 0 && cert_K(lr, t.rslen, kMaxHaplen) <= kCertMax) {
-            rec[t.rslen] |= kMayPredict;
-            lrf = (float)lr;
-            if ((double)lrf < lr) lrf = std::nextafterf(lrf, 1.f);
-          }
-          std::memcpy(rec + 5 * (size_t)t.rslen, &lrf, sizeof(float));
-          read_at.emplace(rk, roff);
+        roff = (uint32_t)pool.size();
+        pool.resize(pool.size() + 5 * (size_t)t.rslen + sizeof(float));  // and the certificate's log(rho)
+        uint8_t *rec = pool.data() + roff;
+        for (int r = 0; r < t.rslen; r++) {
+          rec[r] = read_match_mask(base_code(t.rs[r]));
+          rec[t.rslen + r] = (uint8_t)t.q[r];
+          rec[2 * t.rslen + r] = (uint8_t)t.i[r];
+          rec[3 * t.rslen + r] = (uint8_t)t.d[r];
+          rec[4 * t.rslen + r] = (uint8_t)t.c[r];
         }
-      }
-      last_rk = rk;
-      last_roff = roff;
-      const HapKey hk{t.hap, t.haplen};
-      HapSlot &hs = hcache[(((uintptr_t)t.hap) >> 4) & 255];
-      uint32_t id;
-      if (hs.h == t.hap && hs.len == t.haplen) {
-        id = hs.id;
-      } else {
-        auto hi = hap_at.find(hk);
-        if (hi != hap_at.end()) {
-          id = hi->second;
-        } else {
-          id = (uint32_t)C.hap_off.size();
-          const uint32_t hoff = (uint32_t)pool.size();
-          pool.resize(pool.size() + (size_t)t.haplen);
-          for (int c = 0; c < t.haplen; c++) pool[hoff + c] = base_code(t.hap[c]);
-          hap_at.emplace(hk, id);
-          C.hap_off.push_back(hoff);
-          C.hap_key.push_back(hk);
+        // the early exit's gate: bit 7 of every row's match mask (select_dist reads bits 0..6)
+        if (exit_growth(tables.hf, rec, t.rslen) <= kExitGrowthMax)
+          for (int r = 0; r < t.rslen; r++) rec[r] |= kMayExit;
+        // the predictor's certificate: bit 7 of the first quality byte (the kernels read bits 0..6)
+        if (t.rslen > 0) rec[t.rslen] &= 127;
+        // (a call that will not be predicted, see batch_fill's may_predict, certifies nothing)
+        const double lr = cert_wanted ? cert_log_rho(tables.cert, rec + t.rslen, rec + 2 * t.rslen, rec + 3 * t.rslen,
+                                                     rec + 4 * t.rslen, t.rslen)
+                                      : std::numeric_limits<double>::infinity();
+        float lrf = 0.f;
+        if (t.rslen > 0 && cert_K(lr, t.rslen, kMaxHaplen) <= kCertMax) {
+          rec[t.rslen] |= kMayPredict;
+          lrf = (float)lr;
+          if ((double)lrf < lr) lrf = std::nextafterf(lrf, 1.f);
         }
-        hs.h = t.hap;
-        hs.len = t.haplen;
-        hs.id = id;
+        std::memcpy(rec + 5 * (size_t)t.rslen, &lrf, sizeof(float));
+        read_at.emplace(rk, roff);
       }
-      hid[k] = id;  // local until the merge
-      // read offset chunk-relative and the local haplotype id until the merge
-      desc[k] = TcDesc{roff, 0, (uint32_t)t.rslen | ((uint32_t)t.haplen << 16), (uint32_t)k};
-      C.cells += (int64_t)t.rslen * t.haplen;
     }
-  };
+    last_rk = rk;
+    last_roff = roff;
+    const HapKey hk{t.hap, t.haplen};
+    HapSlot &hs = hcache[(((uintptr_t)t.hap) >> 4) & 255];
+    uint32_t id;
+    if (hs.h == t.hap && hs.len == t.haplen) {
+      id = hs.id;
+    } else {
+      auto hi = hap_at.find(hk);
+      if (hi != hap_at.end()) {
+        id = hi->second;
+      } else {
+        id = (uint32_t)C.hap_off.size();
+        const uint32_t hoff = (uint32_t)pool.size();
+        pool.resize(pool.size() + (size_t)t.haplen);
+        for (int c = 0; c < t.haplen; c++) pool[hoff + c] = base_code(t.hap[c]);
+        hap_at.emplace(hk, id);
+        C.hap_off.push_back(hoff);
+        C.hap_key.push_back(hk);
+      }
+      hs.h = t.hap;
+      hs.len = t.haplen;
+      hs.id = id;
+    }
+    hid[k] = id;  // local until the merge
+    // read offset chunk-relative and the local haplotype id until the merge
+    desc[k] = TcDesc{roff, 0, (uint32_t)t.rslen | ((uint32_t)t.haplen << 16), (uint32_t)k};
+    C.cells += (int64_t)t.rslen * t.haplen;
+  }
+}
+
+// Pack: deduplicate reads and haplotypes by pointer (the driver shares them across the R x H cross
+// product, PairHMMUnitTest.cpp:564-579), convert bases to codes once. Big jobs pack in contiguous chunks
+// on several threads, each with its own pool and maps (a read shared across a chunk edge is stored once
+// per chunk).
+int pack_testcases(const gb_testcase *tcs, int n, int nth, bool cert_wanted, const PackTables &tables,
+                   std::vector<std::vector<uint8_t>> &pools, TcDesc *desc, uint32_t *hid,
+                   std::vector<PackChunk> *chunks) {
+  std::vector<PackChunk> &ch = *chunks;
+  ch.assign(nth, PackChunk{});
   for (int t = 0; t < nth; t++) {
     ch[t].lo = (int)((int64_t)n * t / nth);
     ch[t].hi = (int)((int64_t)n * (t + 1) / nth);
-    ch[t].pool = &b->pools[t];
+    ch[t].pool = &pools[t];
     ch[t].pool->clear();
   }
-  if (int st = gb::parallel("gb_phmm_batch_create", nth, [&](int t) { pack_chunk(ch[t]); })) return st;
-  clk.mark("pack");
-  // merge: chunk pool bases, global haplotype ids (first appearance), one pool in the staging buffer
+  return gb::parallel("gb_phmm_batch_create", nth,
+                      [&](int t) { pack_chunk(tcs, ch[t], cert_wanted, tables, desc, hid); });
+}
+
+int merged_pool_bytes(const std::vector<PackChunk> &chunks, size_t *pool_bytes) {
+  size_t sum = 0;
+  for (const PackChunk &C : chunks) sum += C.pool->size();
+  GB_ARG(sum < (1ull << 32), "batch pool exceeds 4 GiB");
+  *pool_bytes = std::max<size_t>(gb::round_up<size_t>(sum, 16), 16);
+  return GB_OK;
+}
+
+// Merge: chunk pool bases, global haplotype ids in first-appearance order, which is the id order a
+// single pass gives, one pool.
+int merge_pools(const std::vector<PackChunk> &ch, TcDesc *desc, uint32_t *hid, uint8_t *h_pool, size_t pool_bytes,
+                std::vector<uint32_t> *hap_off_of_, int64_t *cells) {
+  const int nth = (int)ch.size();
+  std::vector<uint32_t> &hap_off_of = *hap_off_of_;
+  hap_off_of.clear();
   std::vector<size_t> base(nth + 1, 0);
   for (int t = 0; t < nth; t++) base[t + 1] = base[t] + ch[t].pool->size();
-  GB_ARG(base[nth] < (1ull << 32), "batch pool exceeds 4 GiB");
-  const size_t pool_bytes = std::max<size_t>(gb::round_up<size_t>(base[nth], 16), 16);
-  const StageLayout L(nn, pool_bytes);
-  if (int st = stage_reserve(b, L.total, sizeof(TcDesc) * nn)) return st;
-  desc = (TcDesc *)b->h_stage.get();
-  uint8_t *h_pool = b->h_stage + L.o_pool;
-  std::vector<uint32_t> hap_off_of;
   std::vector<std::vector<uint32_t>> gid(nth);
   {
     std::unordered_map<HapKey, uint32_t, KeyHash> hap_at;
@@ -2082,8 +1796,8 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
       }
     }
   }
-  int64_t cells = 0;
-  for (int t = 0; t < nth; t++) cells += ch[t].cells;
+  *cells = 0;
+  for (int t = 0; t < nth; t++) *cells += ch[t].cells;
   auto merge_chunk = [&](int t) {
     if (!ch[t].pool->empty()) std::memcpy(h_pool + base[t], ch[t].pool->data(), ch[t].pool->size());
     for (int k = ch[t].lo; k < ch[t].hi; k++) {
@@ -2094,15 +1808,24 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   };
   if (int st = gb::parallel("gb_phmm_batch_create", nth, merge_chunk)) return st;
   std::memset(h_pool + base[nth], 0, pool_bytes - base[nth]);
-  clk.mark("merge");
-  // Stacks (phmm_stack): testcases grouped by haplotype, stacked up to kStackRows rows (R + 2 per
-  // testcase) and 64 testcases; longest-processing-time first (the dispatcher hands out workgroups
-  // in grid order).
-  uint32_t *order = (uint32_t *)(b->h_stage + L.o_tc);  // the stacks' testcase lists
+  return GB_OK;
+}
+
+// Plan. Stacks (phmm_stack): testcases grouped by haplotype, stacked up to stack_rows rows (R + 2 per
+// testcase) and 64 testcases; longest-processing-time first (the dispatcher hands out workgroups in grid
+// order).
+Plan plan_stacks(const TcDesc *desc, int n, const uint32_t *hid, int n_haps, const Knobs &knobs, int cus,
+                 uint32_t *order, Stack *stacks, uint64_t *key, Stack *h_stacks, HostClock &clk) {
+  auto rows_of = [&](uint32_t at) { return (int)(desc[order[at]].dims & 0xffff) + 2; };  // of order[at], stacked
+  auto stack_rows_of = [&](const Stack &S) {
+    int rows = 0;
+    for (uint32_t t = 0; t < S.count; t++) rows += rows_of(S.first + t);
+    return rows;
+  };
   {  // counting sort by haplotype (stable: testcases keep their order within a haplotype)
-    std::vector<int> first(hap_off_of.size() + 1, 0);
+    std::vector<int> first((size_t)n_haps + 1, 0);
     for (int k = 0; k < n; k++) first[hid[k] + 1]++;
-    for (size_t h = 0; h < hap_off_of.size(); h++) first[h + 1] += first[h];
+    for (int h = 0; h < n_haps; h++) first[h + 1] += first[h];
     for (int k = 0; k < n; k++) order[first[hid[k]]++] = (uint32_t)k;
   }
   clk.mark("haplotype order");
@@ -2116,113 +1839,71 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   // 2.75 M rows, 512 (0.83 ms against 0.90 at 1024).
   int64_t total_rows = 0;
   for (int k = 0; k < n; k++) total_rows += (int64_t)(desc[k].dims & 0xffff) + 2;
-  // one row per lane: the two-row form (phmm_forward2) issues 125 VALU per 8 cells against 67 per 4
-  // but measured slower at every register budget (f32 19.1 ms; two rows 19.8 / 20.6 / 20.9 ms at 5 /
-  // 6 / 8 waves per SIMD, profiles/r05b_phmm_rpl_ab.log); GB_PHMM_RPL=2 selects it for A/B probes
-  b->rpl = 1;
-  if (const char *e = getenv("GB_PHMM_RPL")) b->rpl = atoi(e) == 2 ? 2 : 1;
-  b->w2 = 0;
-  if (const char *e = getenv("GB_PHMM_W2")) b->w2 = atoi(e);
-  // work units per stack in the f64 pass: in stack order, two units per stack took the 1/8 shard's
-  // f64 pass 2.28 -> 2.00 ms (profiles/r05e_phmm_f64_parts.log); ordered by cost (f64_plan) one unit
-  // per stack is best: the shard 1.93 (stack order, two) -> 1.82 (plan, two) -> 1.78 ms (plan, one), the
-  // whole job 13.19 -> 13.07 -> 12.95 ms (profiles/r06x_phmm_f64_plan.log)
-  b->f64_parts = 1;
-  if (const char *e = getenv("GB_PHMM_F64_PARTS")) b->f64_parts = std::max(1, std::min(kMaxF64Parts, atoi(e)));
-  b->f64_plan = true;
-  if (const char *e = getenv("GB_PHMM_F64_PLAN")) b->f64_plan = atoi(e) != 0;
-  // the f32 pass drops a testcase's remaining rows once its crossing mass proves it falls back to f64
-  // (phmm_stack kExit): f32 pass 19.05 -> 18.40 ms, step +2.0 % (profiles/r05zzi_phmm_exit_ab.log);
-  // finals, raw f64 and the fallback choice unchanged, a dropped testcase's raw f32 reads 0
-  b->f32_exit = true;
-  if (const char *e = getenv("GB_PHMM_EXIT")) b->f32_exit = atoi(e) != 0;
-  // rolled stripes (phmm_rolled) in both passes
-  b->roll = true;
-  if (const char *e = getenv("GB_PHMM_ROLL")) b->roll = atoi(e) != 0;
-  // the fallback predictor (phmm_predict): on; GB_PHMM_PREDICT=0 off, =all every certified testcase with
-  // the gate off (tests: every passing testcase then takes the verify -> redo path), =open the estimate
-  // with the gate off (tests of jobs too small for the gate's sample)
-  b->predict = 1;
-  if (const char *e = getenv("GB_PHMM_PREDICT"))
-    b->predict = strcmp(e, "all") == 0 ? 2 : strcmp(e, "open") == 0 ? 3 : (atoi(e) != 0 ? 1 : 0);
-  const bool roll = b->roll && b->rpl == 1;
   int stack_rows = kStackRows;
-  if (total_rows / stack_rows < 4ll * 32 * b->cus) stack_rows = 1024;
-  if (stack_rows == 1024 && total_rows / stack_rows < 16ll * b->cus) stack_rows = 512;
+  if (total_rows / stack_rows < 4ll * 32 * cus) stack_rows = 1024;
+  if (stack_rows == 1024 && total_rows / stack_rows < 16ll * cus) stack_rows = 512;
   // a small call (one of the reference's per-batch calls) is its longest stack: below 2 stacks per
   // SIMD the stacks shrink further, to 128 rows
-  while (stack_rows > 128 && total_rows / stack_rows < 8ll * b->cus) stack_rows /= 2;
-  if (const char *e = getenv("GB_PHMM_STACK_ROWS")) stack_rows = std::max(1, atoi(e));  // probes
+  while (stack_rows > 128 && total_rows / stack_rows < 8ll * cus) stack_rows /= 2;
+  if (knobs.stack_rows_forced) stack_rows = knobs.stack_rows_forced;
   // sort keys: long-haplotype stacks last (they run on the kLong kernels), then decreasing cost,
   // then stack index (so the order is the stable one)
-  Stack *stacks = b->stacks.data();
-  uint64_t *key = b->skeys.data(), *key2 = key + nn;
-  int ns_all = 0, n_long = 0, max_h_short = 0, max_h_long = 0;
-  const int sh = b->rpl == 2 ? kRows2 : kWave;  // stripe height of the f32 pass
+  uint64_t *key2 = key + n;
+  Plan P;
   for (int k = 0; k < n;) {
     const uint32_t h = desc[order[k]].hap_off;
     const int C = (int)(desc[order[k]].dims >> 16);
     Stack S{(uint32_t)k, 0, h, (uint32_t)C};
     int rows = 0;
     while (k < n && desc[order[k]].hap_off == h && S.count < (uint32_t)kWave &&
-           (S.count == 0 || rows + (int)(desc[order[k]].dims & 0xffff) + 2 <= stack_rows)) {
-      rows += (int)(desc[order[k]].dims & 0xffff) + 2;
+           (S.count == 0 || rows + rows_of(k) <= stack_rows)) {
+      rows += rows_of(k);
       S.count++;
       k++;
     }
     const bool is_long = C > kLdsHaplen;
     if (is_long) {
-      n_long++;
-      max_h_long = std::max(max_h_long, C);
+      P.n_long++;
+      P.max_h_long = std::max(P.max_h_long, C);
     } else {
-      max_h_short = std::max(max_h_short, C);
+      P.max_h_short = std::max(P.max_h_short, C);
     }
-    const uint64_t cost = std::min<uint64_t>(stack_steps(rows, C, sh, false), 0x7fffffffu);
-    key[ns_all] = ((uint64_t)is_long << 63) | ((0x7fffffffu - cost) << 32) | (uint32_t)ns_all;
-    stacks[ns_all++] = S;
+    const uint64_t cost = std::min<uint64_t>(stack_steps(rows, C, kWave, false), 0x7fffffffu);
+    key[P.ns_all] = ((uint64_t)is_long << 63) | ((0x7fffffffu - cost) << 32) | (uint32_t)P.ns_all;
+    stacks[P.ns_all++] = S;
   }
   clk.mark("stack build");
   // LSD radix sort of the keys' upper 32 bits, 8 bits a pass (the low 32 bits are the index)
-  auto sort_keys = [&](int ns_all) {
+  auto sort_keys = [&](int ns) {
     uint32_t cnt[256];
     for (int shift = 32; shift < 64; shift += 8) {
-      const uint64_t d0 = ns_all ? (key[0] >> shift) & 255 : 0;
+      const uint64_t d0 = ns ? (key[0] >> shift) & 255 : 0;
       bool same = true;
-      for (int k = 1; k < ns_all && same; k++) same = ((key[k] >> shift) & 255) == d0;
+      for (int k = 1; k < ns && same; k++) same = ((key[k] >> shift) & 255) == d0;
       if (same) continue;
       std::memset(cnt, 0, sizeof(cnt));
-      for (int k = 0; k < ns_all; k++) cnt[(key[k] >> shift) & 255]++;
+      for (int k = 0; k < ns; k++) cnt[(key[k] >> shift) & 255]++;
       for (uint32_t d = 0, sum = 0; d < 256; d++) {
         const uint32_t c = cnt[d];
         cnt[d] = sum;
         sum += c;
       }
-      for (int k = 0; k < ns_all; k++) key2[cnt[(key[k] >> shift) & 255]++] = key[k];
+      for (int k = 0; k < ns; k++) key2[cnt[(key[k] >> shift) & 255]++] = key[k];
       std::swap(key, key2);
     }
   };
-  sort_keys(ns_all);
-  Stack *h_stacks = (Stack *)(b->h_stage + L.o_stk);
-  for (int k = 0; k < ns_all; k++) h_stacks[k] = stacks[(uint32_t)key[k]];
+  sort_keys(P.ns_all);
+  for (int k = 0; k < P.ns_all; k++) h_stacks[k] = stacks[(uint32_t)key[k]];
   // Tail split: the stacks holding the last 10 % of the LPT order's cost are cut into stacks of at
   // most 512 rows (taller stacks waste less on the anti-diagonal fill; shorter ones let the grid's
   // last waves end together). Measured (tools/phmm_shard_probe.py, profiles/r06h/r06i): the 'large'
   // job 31.93-32.00 -> 31.65 ms, its 1/8 shard 4.47-4.49 -> 4.41-4.46 ms; 5 / 15 / 20 / 30 % and
-  // 128 / 256 / 384-row pieces no better on the job. GB_PHMM_TAIL=frac:rows (0 = off) for probes.
-  double frac = stack_rows > 512 ? 0.10 : 0.0;
-  int trows = 512;
-  if (const char *te = getenv("GB_PHMM_TAIL")) {
-    frac = atof(te);
-    const char *cm = strchr(te, ':');
-    if (cm) trows = std::max(1, atoi(cm + 1));
-  }
+  // 128 / 256 / 384-row pieces no better on the job.
+  const double frac = knobs.tail_frac >= 0 ? knobs.tail_frac : (stack_rows > 512 ? 0.10 : 0.0);
+  const int trows = knobs.tail_rows;
   if (frac > 0) {
-    const int ns_short = ns_all - n_long;
-    auto cost_of = [&](const Stack &S) -> uint64_t {
-      int rows = 0;
-      for (uint32_t t = 0; t < S.count; t++) rows += (int)(desc[order[S.first + t]].dims & 0xffff) + 2;
-      return stack_steps(rows, (int)S.C, sh, false);
-    };
+    const int ns_short = P.ns_all - P.n_long;
+    auto cost_of = [&](const Stack &S) -> uint64_t { return stack_steps(stack_rows_of(S), (int)S.C, kWave, false); };
     uint64_t total = 0;
     for (int k = 0; k < ns_short; k++) total += cost_of(h_stacks[k]);
     uint64_t acc = 0;
@@ -2233,33 +1914,31 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
       const Stack S = h_stacks[k];
       uint32_t t = 0;
       while (t < S.count) {
-        Stack P{S.first + t, 0, S.hap_off, S.C};
+        Stack Q{S.first + t, 0, S.hap_off, S.C};
         int rows = 0;
-        while (t < S.count && (P.count == 0 || rows + (int)(desc[order[S.first + t]].dims & 0xffff) + 2 <= trows)) {
-          rows += (int)(desc[order[S.first + t]].dims & 0xffff) + 2;
-          P.count++;
+        while (t < S.count && (Q.count == 0 || rows + rows_of(S.first + t) <= trows)) {
+          rows += rows_of(S.first + t);
+          Q.count++;
           t++;
         }
-        pieces.push_back({stack_steps(rows, (int)S.C, sh, false), P});
+        pieces.push_back({stack_steps(rows, (int)S.C, kWave, false), Q});
       }
     }
     std::stable_sort(pieces.begin(), pieces.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-    std::vector<Stack> longs(h_stacks + ns_short, h_stacks + ns_all);
+    std::vector<Stack> longs(h_stacks + ns_short, h_stacks + P.ns_all);
     int k = t0;
     for (const auto &pc : pieces) h_stacks[k++] = pc.second;
     for (const auto &ls : longs) h_stacks[k++] = ls;
-    ns_all = k;
+    P.ns_all = k;
   }
   // Which testcases share a stack is decided above by the fill-per-stripe cost, whatever the sweep (a
   // dropped testcase's raw f32 depends on where the early exit's stripes fall in its stack). The launch
   // order of the LDS stacks is by the cost of the sweep they take: the rolled one's wave steps.
-  if (roll) {
-    const int ns_short = ns_all - n_long;
+  if (knobs.roll) {
+    const int ns_short = P.ns_all - P.n_long;
     for (int k = 0; k < ns_short; k++) {
       const Stack &S = h_stacks[k];
-      int rows = 0;
-      for (uint32_t t = 0; t < S.count; t++) rows += (int)(desc[order[S.first + t]].dims & 0xffff) + 2;
-      const uint64_t cost = std::min<uint64_t>(stack_steps(rows, (int)S.C, sh, true), 0x7fffffffu);
+      const uint64_t cost = std::min<uint64_t>(stack_steps(stack_rows_of(S), (int)S.C, kWave, true), 0x7fffffffu);
       key[k] = ((0x7fffffffu - cost) << 32) | (uint32_t)k;
       stacks[k] = S;
     }
@@ -2267,12 +1946,64 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
     for (int k = 0; k < ns_short; k++) h_stacks[k] = stacks[(uint32_t)key[k]];
   }
   clk.mark("stacks");
+  return P;
+}
+
+}  // namespace phmm
+}  // namespace gb
+
+namespace {
+
+// Fill: pack the testcases (deduplicated reads/haplotypes, stacks in LPT order) into b's pinned staging
+// buffer and upload them, growing its buffers when they are too small; b's stream/events exist
+// already. threads: host threads of the pack and merge phases (0: up to 8 from pack_min testcases).
+// validated: the caller has run validate_testcases over the whole call (compute_pipelined, whose
+// chunks would otherwise name a testcase by its index in the chunk). Inputs are validated first
+// (sequentially, so the error names the first bad testcase). Descriptors, stack lists, stacks and pool
+// are written straight into the pinned staging buffer.
+int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0, bool validated = false) {
+  HostClock clk;
+  if (!validated)
+    if (int st = validate_testcases(tcs, n)) return st;
+  clk.mark("validate");
+  const Knobs K = b->knobs = read_knobs();
+  int nth = n >= K.pack_min ? (int)std::max(1u, std::min(8u, std::thread::hardware_concurrency())) : 1;
+  if (threads > 0) nth = std::max(1, std::min(threads, n / 4096));
+  nth = std::max(1, std::min(nth, n / 2048));
+  const size_t nn = std::max(n, 1);
+  host_reserve(b, nn, 0, nth);
+  // descriptors are written by the pack (a bigger pool than guessed grows the buffer after it)
+  if (int st = stage_reserve(b, StageLayout(nn, 32 * nn).total)) return st;
+  uint32_t *hid = b->hid.data();  // dense haplotype index of each testcase (stack grouping)
+  // one-shot calls below kPredMinCells do without the predictor (phmm_predict, "Gate")
+  int64_t pre_cells = 0;
+  for (int k = 0; k < n; k++) pre_cells += (int64_t)tcs[k].rslen * tcs[k].haplen;
+  const bool cert_wanted = b->resident || pre_cells >= kPredMinCells;
+  std::vector<PackChunk> ch;
+  if (int st = pack_testcases(tcs, n, nth, cert_wanted, *g_host, b->pools, (TcDesc *)b->h_stage.get(), hid, &ch))
+    return st;
+  clk.mark("pack");
+  size_t pool_bytes = 0;
+  if (int st = merged_pool_bytes(ch, &pool_bytes)) return st;
+  const StageLayout L(nn, pool_bytes);
+  if (int st = stage_reserve(b, L.total, sizeof(TcDesc) * nn)) return st;
+  TcDesc *desc = (TcDesc *)b->h_stage.get();
+  uint32_t *order = (uint32_t *)(b->h_stage + L.o_tc);  // the stacks' testcase lists
+  Stack *h_stacks = (Stack *)(b->h_stage + L.o_stk);
+  uint8_t *h_pool = b->h_stage + L.o_pool;
+  std::vector<uint32_t> hap_off_of;
+  int64_t cells = 0;
+  if (int st = merge_pools(ch, desc, hid, h_pool, pool_bytes, &hap_off_of, &cells)) return st;
+  clk.mark("merge");
+  const Plan P = plan_stacks(desc, n, hid, (int)hap_off_of.size(), K, b->cus, order, b->stacks.data(),
+                             b->skeys.data(), h_stacks, clk);
+  const int ns_short = P.ns_all - P.n_long;
   if (int st = batch_reserve(b, n, pool_bytes)) return st;
-  if (n_long) {
+  if (P.n_long) {
     // records + codes of one long stack per workgroup of the persistent kLong grid
-    b->long_grid = std::min(n_long, b->f64_grid);
-    b->scratch_stride = gb::round_up<size_t>(sizeof(Brec<double>) * (size_t)(max_h_long + kBndPad + kRecPad) +
-                                                 (size_t)(max_h_long + kBndPad + kWave) + 16, 256);
+    b->long_grid = std::min(P.n_long, b->f64_grid);
+    b->scratch_stride = gb::round_up<size_t>(sizeof(Brec<double>) * (size_t)(P.max_h_long + kBndPad + kRecPad) +
+                                                 (size_t)(P.max_h_long + kBndPad + kWave) + 16, 256);
     const size_t need = b->scratch_stride * (size_t)b->long_grid;
     if (int st = b->d_scratch.reserve(need)) return st;
   }
@@ -2282,17 +2013,15 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   if (n) {
     GB_HIP(hipMemcpyAsync(b->d_desc, desc, sizeof(TcDesc) * n, hipMemcpyHostToDevice, b->stream));
     GB_HIP(hipMemcpyAsync(b->d_stk_tc, order, sizeof(uint32_t) * n, hipMemcpyHostToDevice, b->stream));
-    GB_HIP(hipMemcpyAsync(b->d_stacks, h_stacks, sizeof(Stack) * ns_all, hipMemcpyHostToDevice, b->stream));
+    GB_HIP(hipMemcpyAsync(b->d_stacks, h_stacks, sizeof(Stack) * P.ns_all, hipMemcpyHostToDevice, b->stream));
   }
   GB_HIP(hipMemcpyAsync(b->d_pool, h_pool, pool_bytes, hipMemcpyHostToDevice, b->stream));
   // the predictor's gate (phmm_predict): sampled here, behind the uploads, and read at the fill's own
   // synchronisation; one-shot calls below kPredMinCells do without the predictor
-  const int ns_short = ns_all - n_long;
-  const bool may_predict = b->predict && b->f32_exit && b->rpl == 1 && ns_short > 0 &&
-                           cert_wanted;
+  const bool may_predict = K.predict && K.f32_exit && ns_short > 0 && cert_wanted;
   int gate[2] = {0, 0};
-  b->gate_open = may_predict && b->predict >= 2;
-  if (may_predict && b->predict == 1) {
+  b->gate_open = may_predict && K.predict >= 2;
+  if (may_predict && K.predict == 1) {
     GB_HIP(hipMemsetAsync(b->d_count, 0, kCountWords * sizeof(int), b->stream));
     const int sg = std::min(ns_short, b->cus * 16);
     hipLaunchKernelGGL(phmm_predict, dim3(sg), dim3(kWave), 0, b->stream, (const Stack *)b->d_stacks, ns_short,
@@ -2304,12 +2033,12 @@ int batch_fill(gb_phmm_batch *b, const gb_testcase *tcs, int n, int threads = 0,
   GB_HIP(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next fill
   b->gate_n = gate[0];
   b->gate_pred = gate[1];
-  if (may_predict && b->predict == 1) b->gate_open = (int64_t)gate[1] * kGateDen >= (int64_t)gate[0] && gate[1] > 0;
+  if (may_predict && K.predict == 1) b->gate_open = (int64_t)gate[1] * kGateDen >= (int64_t)gate[0] && gate[1] > 0;
   clk.mark("upload");
   b->n = n;
-  b->nstacks = ns_all - n_long;
-  b->n_long = n_long;
-  b->max_haplen = max_h_short;
+  b->nstacks = ns_short;
+  b->n_long = P.n_long;
+  b->max_haplen = P.max_h_short;
   b->cells = cells;
   b->ran = false;
   return GB_OK;
@@ -2323,9 +2052,9 @@ int batch_new(DeviceTables *tabs, gb_phmm_batch **out) {
   b->f64_grid = cus * 16;
   if (const char *e = getenv("GB_PHMM_F64_GRID")) b->f64_grid = cus * std::max(1, std::min(32, atoi(e)));  // probe
   b->cus = cus;
-  hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+  hipError_t e = b->stream.create();
   for (auto &ev : b->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = ev.create();
   if (e != hipSuccess) {
     gb::set_error("gb_phmm_batch_create: %s", hipGetErrorString(e));
     gb_phmm_batch_destroy(b);
@@ -2503,7 +2232,7 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
   GB_HIP(hipEventRecord(b->ev[0], b->stream));
   GB_HIP(hipMemsetAsync(b->d_count, 0, kCountWords * sizeof(int), b->stream));
   // (a run with the predictor zeroes d_rd together with d_pred and d_redo behind it)
-  const bool predict = n > 0 && b->gate_open && b->f32_exit && !b->force_f64 && b->rpl == 1 && b->nstacks > 0;
+  const bool predict = n > 0 && b->gate_open && b->knobs.f32_exit && !b->force_f64 && b->nstacks > 0;
   GB_HIP(hipMemsetAsync(b->d_rd, 0, predict ? b->pred_bytes : sizeof(double) * std::max(n, 1), b->stream));
   if (n > 0) {
     const size_t rec = (size_t)(b->max_haplen + kBndPad + kRecPad), codes = (size_t)(b->max_haplen + kBndPad + kWave);
@@ -2513,7 +2242,7 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
     auto f64k = phmm_forward<double, true>;
     const int ns = b->nstacks, nl = b->n_long;
     const Stack *d_long = b->d_stacks + ns;
-    if (b->f32_exit) f32k = phmm_forward<float, false, false, true>;
+    if (b->knobs.f32_exit) f32k = phmm_forward<float, false, false, true>;
     // the fallback predictor, on the exit's switch too (GB_PHMM_EXIT=0 keeps every raw f32), when the
     // fill's sample opened the gate; the f32 pass then leaves the predicted testcases out
     const uint8_t *skip = predict ? b->d_pred : nullptr;
@@ -2521,22 +2250,15 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
     if (predict) {
       const int pg = std::min(ns, b->cus * 16);
       hipLaunchKernelGGL(phmm_predict, dim3(pg), dim3(kWave), 0, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
-                         b->d_pool, b->d_rf, b->d_pred, b->d_count, b->predict == 2 ? (int)kPredAll : (int)kPredOpen);
+                         b->d_pool, b->d_rf, b->d_pred, b->d_count, b->knobs.predict == 2 ? (int)kPredAll : (int)kPredOpen);
       GB_HIP(hipGetLastError());
     }
     if (!b->force_f64) {
-      if (ns > 0 && b->rpl == 2) {
-        const size_t lds_f2 = sizeof(Brec<float>) * (size_t)(b->max_haplen + kBndPad2 + kRecPad) +
-                              (size_t)(b->max_haplen + kBndPad2 + kCodePad2) + 16;
-        auto k2 = b->w2 == 8 ? phmm_forward2<8> : b->w2 == 6 ? phmm_forward2<6> : phmm_forward2<0>;
-        hipLaunchKernelGGL(k2, dim3(ns), dim3(kWave), lds_f2, b->stream, b->d_stacks, b->d_stk_tc,
-                           b->d_desc, b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf);
-      } else if (ns > 0) {
+      if (ns > 0)
         hipLaunchKernelGGL(f32k, dim3(ns), dim3(kWave), lds_f, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                            b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf, (const float *)nullptr,
-                           b->d_count, b->roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr,
+                           b->d_count, b->knobs.roll ? 1 << 16 : 0, (uint8_t *)nullptr, (size_t)0, (const uint32_t *)nullptr,
                            skip, 0, (const float *)nullptr, (uint8_t *)nullptr);
-      }
       if (nl > 0)
         hipLaunchKernelGGL((phmm_forward<float, false, true>), dim3(b->long_grid), dim3(kWave), 0, b->stream, d_long,
                            nl, b->d_stk_tc, b->d_desc, b->d_pool, dev_tab<float>(t->f, t->hf.init_const), b->d_rf,
@@ -2547,20 +2269,20 @@ int gb_phmm_batch_run(gb_phmm_batch *b) {
     GB_HIP(hipEventRecord(b->ev[1], b->stream));
     // f64 fallback: persistent grid over the stacks, each recomputing its flagged testcases
     if (ns > 0) {
-      const int nunits = ns * b->f64_parts;
+      const int nunits = ns * b->knobs.f64_parts;
       const int g64 = std::min(nunits, b->f64_grid);
-      if (b->f64_plan) {
+      if (b->knobs.f64_plan) {
         const dim3 pg((unsigned)((nunits + 255) / 256)), pb(256);
-        hipLaunchKernelGGL(f64_plan, pg, pb, 0, b->stream, b->d_stacks, nunits, b->f64_parts, b->d_stk_tc, b->d_desc,
-                           (const float *)b->d_rf, b->force_f64 ? 1 : 0, b->roll ? 1 : 0, b->d_ukey, b->d_count);
+        hipLaunchKernelGGL(f64_plan, pg, pb, 0, b->stream, b->d_stacks, nunits, b->knobs.f64_parts, b->d_stk_tc, b->d_desc,
+                           (const float *)b->d_rf, b->force_f64 ? 1 : 0, b->knobs.roll ? 1 : 0, b->d_ukey, b->d_count);
         hipLaunchKernelGGL(f64_plan_order, pg, pb, 0, b->stream, nunits, (const uint8_t *)b->d_ukey, b->d_count,
                            b->d_units);
       }
       hipLaunchKernelGGL(f64k, dim3(g64), dim3(kWave), lds_d, b->stream, b->d_stacks, ns, b->d_stk_tc, b->d_desc,
                          b->d_pool, dev_tab<double>(t->d, t->hd.init_const), b->d_rd, (const float *)b->d_rf,
-                         b->d_count, (b->force_f64 ? 1 : 0) | (b->f64_parts << 8) | (b->roll ? 1 << 16 : 0),
+                         b->d_count, (b->force_f64 ? 1 : 0) | (b->knobs.f64_parts << 8) | (b->knobs.roll ? 1 << 16 : 0),
                          (uint8_t *)nullptr, (size_t)0,
-                         b->f64_plan ? (const uint32_t *)b->d_units : nullptr, skip, 0,
+                         b->knobs.f64_plan ? (const uint32_t *)b->d_units : nullptr, skip, 0,
                          (const float *)t->f, predict ? b->d_redo : nullptr);
     }
     if (nl > 0)
@@ -2727,7 +2449,7 @@ int gb_phmm_certificate(const gb_testcase *tcs, int n, double *K, uint8_t *certi
   }
   for (int k = 0; k < n; k++) {
     const gb_testcase &t = tcs[k];
-    const double lr = cert_log_rho(*g_cert, (const uint8_t *)t.q, (const uint8_t *)t.i, (const uint8_t *)t.d,
+    const double lr = cert_log_rho(g_host->cert, (const uint8_t *)t.q, (const uint8_t *)t.i, (const uint8_t *)t.d,
                                    (const uint8_t *)t.c, t.rslen);
     if (K) K[k] = cert_K(lr, t.rslen, t.haplen);
     if (certified) certified[k] = cert_K(lr, t.rslen, kMaxHaplen) <= kCertMax ? 1 : 0;
@@ -2738,10 +2460,7 @@ int gb_phmm_certificate(const gb_testcase *tcs, int n, double *K, uint8_t *certi
 int gb_phmm_batch_destroy(gb_phmm_batch *b) {
   if (!b) return GB_OK;
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  for (auto e : b->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
+  delete b;  // the events, the stream and the buffers go with it
   return GB_OK;
 }
 
@@ -2795,7 +2514,7 @@ int gb_phmm_compute_f32(const gb_testcase *tcs, int n, float *raw_f) {
   if (!b) return st;
   b->force_f64 = false;
   if ((st = batch_fill(b, tcs, n))) return st;
-  b->f32_exit = false;  // every testcase's f32 probability in full, also those that fall back
+  b->knobs.f32_exit = false;  // every testcase's f32 probability in full, also those that fall back
   st = gb_phmm_batch_run(b);
   if (!st) st = gb_phmm_batch_sync(b);
   if (!st) st = gb_phmm_batch_results(b, nullptr, raw_f, nullptr, nullptr, nullptr);

@@ -113,9 +113,9 @@ def test_bsw_after_poison(poison, monkeypatch, tail):
         b.close()
 
 
-@pytest.mark.parametrize("knob", ["", "GB_PHMM_RPL=2", "GB_PHMM_EXIT=0"])
+@pytest.mark.parametrize("knob", ["", "GB_PHMM_EXIT=0"])
 def test_phmm_after_poison(poison, monkeypatch, knob):
-    """phmm_forward<float> (default: with the early exit; the two-row kernel; without the exit) and the
+    """phmm_forward<float> (default: with the early exit; without the exit) and the
     f64 fallback's persistent grid, on a job with partial stripes and both passes."""
     import ctypes as ct
     from conftest import assert_phmm_exact

@@ -258,20 +258,6 @@ def test_pipelined_big_pool_bit_exact(phmm, monkeypatch):
     assert_exact(phmm.compute_likelihoods_both(ta), oracle_run(ta))
 
 
-def test_rows_per_lane_ab_identical(phmm, monkeypatch):
-    """The f32 pass with one row per lane (default) and with two (GB_PHMM_RPL=2) agree bit for bit
-    on a job with many stacks, partial stripes and both passes."""
-    rng = np.random.default_rng(29)
-    ta = TestcaseArray.from_batches([gen.phmm_batch(rng, 50, 20) for _ in range(4)])
-    monkeypatch.setenv("GB_PHMM_EXIT", "0")  # the two-row kernel has no early exit: compare every raw f32
-    outs = []
-    for rpl in ("1", "2"):
-        monkeypatch.setenv("GB_PHMM_RPL", rpl)
-        outs.append(phmm.compute_likelihoods_both(ta))
-    for a, b in zip(outs[0][:3], outs[1][:3]):
-        assert (bits(a) == bits(b)).all()
-
-
 @pytest.mark.parametrize("where", ["chunk2", "last"])
 def test_pipelined_bad_testcase_reports_its_index(phmm, monkeypatch, where):
     """A bad testcase in a later chunk of a pipelined call fails the whole call before any device

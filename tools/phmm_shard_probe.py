@@ -25,8 +25,7 @@ if os.environ.get("PHMM_SHARD_ONLY"):  # e.g. under a kernel trace
 for name, ta in jobs:
     for rows in os.environ.get("PHMM_ROWS", "default").split(";"):
         # a setting: "default", a GB_PHMM_STACK_ROWS value, or env assignments "K=V,K=V"
-        for k in ("GB_PHMM_STACK_ROWS", "GB_PHMM_F64_ROWS", "GB_PHMM_RPL", "GB_PHMM_W2", "GB_PHMM_PIPE", "GB_PHMM_TAIL",
-                  "GB_PHMM_F64_REGROUP", "GB_PHMM_F64_PARTS", "GB_PHMM_F64_GRID",
+        for k in ("GB_PHMM_STACK_ROWS", "GB_PHMM_PIPE", "GB_PHMM_TAIL", "GB_PHMM_F64_PARTS", "GB_PHMM_F64_GRID",
                   "GB_PHMM_EXIT", "GB_PHMM_F64_PLAN"):
             os.environ.pop(k, None)
         if "=" in rows:
